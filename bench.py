@@ -63,6 +63,8 @@ def parse():
                                                                'every decode evaluates its table, as the reference does')
     ap.add_argument('--two-cpu-child', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--input-order', default='raster', choices=['raster', 'shuffled'], help='row order of the input cloud (frame config)')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR', help='write what the last timed step computed (decoded coordinates and features, '
+                                                                       'bitstream files) as DIR/<name>.npy, at most 64 MB in all')
     return ap.parse_args()
 
 
@@ -284,15 +286,22 @@ def main():
     # barrier packets around the launch, and the name-pooled dominant kernel has six launches per step — bracketing all of them in every step cost
     # the step 0.3 ms (5 %: the headline ran that much slower than the unbracketed auxiliary measurements of the same process).
     EVENT_EVERY = 4
+    last_outs = None
     for i_step in range(args.steps):
         ops.PROFILE.enabled = dominant is not None and i_step % EVENT_EVERY == 0
         a = time.perf_counter()
-        step(timers)
+        res = step(timers)
         step_ms.append(round((time.perf_counter() - a) * 1e3, 2))
+        if i_step == args.steps - 1:
+            last_outs = res
+        del res
     barrier()
     elapsed = time.perf_counter() - t0
     ops.PROFILE.enabled = False
     torch.cuda.synchronize()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_outs, tmp, prefix=f'r{rank}_' if world > 1 else '', budget=DUMP_BUDGET // world)
+    del last_outs
     bracketed_steps = len(range(0, args.steps, EVENT_EVERY))
     roof = ops.PROFILE.summary(HBM_PEAK_GBS, bracketed_steps, name=dominant) if dominant is not None else None
     if roof is not None:
@@ -628,6 +637,31 @@ def main():
         print(json.dumps(line), flush=True)
     if dist_on:
         dist.destroy_process_group()
+
+
+DUMP_BUDGET = 64 * 10 ** 6 - 2 ** 16          # bytes of array data over all files and ranks (--dump-outputs), headroom for the .npy headers
+
+
+def dump_outputs(out_dir, outs, tmp, prefix='', budget=DUMP_BUDGET):
+    """--dump-outputs: what the caller of the timed path received from the last timed step — per decoded unit its coordinates
+    [N, 4] and features [N, C] (float32: every coordinate is below 2^24), and the bitstream files the step's encode wrote (bytes as
+    float32).  Over `budget` bytes (each of several ranks gets its share of DUMP_BUDGET), every array keeps the same fraction of its
+    rows: a sorted sample drawn with a fixed seed, so the same outputs give the same files."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for i, o in enumerate(outs or []):
+        arrays[f'out{i}_coords'] = o.C.cpu().numpy().astype(np.float32)
+        arrays[f'out{i}_feats'] = o.F.float().cpu().numpy().astype(np.float32)
+    for f in sorted(os.listdir(tmp)):
+        if f.startswith('u_') and f.endswith(('_C.bin', '_F.bin', '_H.bin', '_num_points.bin', '_F.idx')):
+            name = f[2:].replace('.', '_')
+            arrays[name] = np.fromfile(os.path.join(tmp, f), dtype=np.uint8).astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > budget:
+            keep = np.sort(np.random.default_rng(0).choice(len(a), len(a) * budget // total, replace=False))
+            a = a[keep]
+        np.save(os.path.join(out_dir, prefix + name + '.npy'), a)
 
 
 def attach_pmc_traffic(roof):

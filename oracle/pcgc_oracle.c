@@ -6,7 +6,7 @@
  *
  * Parity status
  *   - entropy tables (orc_cdf_float)      pinned to golden G1 (tests/golden/entropy_tables.npz, generated from
- *                                         /root/reference/entropy_model.py:82-149 by tests/golden/make_golden.py)
+ *                                         the reference's entropy_model.py:82-149 by tests/golden/make_golden.py)
  *   - ordering / top-k / PLY / D1         pinned to golden G2..G4 (python side, oracle/pcgc_oracle.py)
  *   - sparse conv family, range coder     "parity unpinned": MinkowskiEngine >=0.5 and torchac 0.9.3 are
  *                                         un-vendored third-party dependencies that are not installable here;

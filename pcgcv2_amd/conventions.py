@@ -1,7 +1,7 @@
 """Switchable ‡ conventions (hard part 1).
 
 Four behaviours of the reference's un-vendored dependencies decide its results at the bit level but are pinned by nothing in
-/root/reference (no ME / torchac source, no test vectors).  Each is ONE switch here, with the same switch in the oracle, so that the
+the reference (no ME / torchac source, no test vectors).  Each is ONE switch here, with the same switch in the oracle, so that the
 day a real MinkowskiEngine run disagrees the convention can be flipped instead of rewritten:
 
   kernel_offset_order  'xyz' (default): offset index k = (dx+1) + 3 (dy+1) + 9 (dz+1), x fastest (ME's kernel_region iteration as

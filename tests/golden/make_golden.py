@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate the golden fixtures under tests/golden/ from the reference implementation.
 
-Runs ONLY in the authoring container (needs /root/reference).  The reference's Python
+Runs only where a checkout of the reference exists: `make_golden.py --reference DIR [g1 ...]`.  The reference's Python
 never travels: this script imports the importable slices of it (with empty stub modules
 for the un-installed third-party packages MinkowskiEngine / torchac / h5py), feeds them
 seeded inputs and stores inputs + outputs as small .npz / .txt data files.
@@ -13,12 +13,18 @@ Fixtures:
   G4 d1_metric.npz        pc_error_d (mpeg-pcc-dmetric 0.13.4) outputs         (pc_error.py:27-74)
   G6 d2_metric.npz        the same binary with `-n infile1` (normal=True): p2plane columns (pc_error.py:40-47,51-53; test.py:74-75)
   G5 state_dict_keys.txt  EntropyBottleneck state_dict names / shapes          (entropy_model.py:59-80)
+  G7 autoencoder_modules.json  the reference's Encoder / Decoder built on pcgcv2_amd.ME: every layer's ME class and
+                          constructor arguments, and the parameter names / shapes they produce        (autoencoder.py)
 """
-import os, sys, types, shutil, subprocess, tempfile
+import os, sys, types, shutil, subprocess, tempfile, json
 import numpy as np
 import torch
 
-REF = '/root/reference'
+if '--reference' not in sys.argv[1:-1]:
+    sys.exit('usage: make_golden.py --reference DIR [g1 g2 g3 g4 g6 g7]')
+_i = sys.argv.index('--reference')
+REF = os.path.abspath(sys.argv[_i + 1])
+del sys.argv[_i:_i + 2]
 OUT = os.path.dirname(os.path.abspath(__file__))
 
 for name in ('torchac', 'h5py', 'MinkowskiEngine'):
@@ -194,8 +200,53 @@ def g6():
     np.savez_compressed(os.path.join(OUT, 'd2_metric.npz'), **out)
 
 
+def g7():
+    """The reference's autoencoder.py, loaded as it is with pcgcv2_amd.ME standing in for MinkowskiEngine: the calls it makes to
+    the facade's layer classes (class name, constructor arguments) and the parameter names / shapes of the module tree it builds."""
+    import importlib.util
+    sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+    import pcgcv2_amd.ME as ME
+    import pcgcv2_amd.data_utils as du
+    facade = types.ModuleType('MinkowskiEngine')
+    facade.__dict__.update({k: v for k, v in vars(ME).items() if not k.startswith('__')})
+
+    def recording(cls):
+        class Rec(cls):
+            def __init__(self, *a, **k):
+                assert not a, f'{cls.__name__}: positional constructor arguments'
+                super().__init__(**k)
+                self.golden_call = dict(k)
+        Rec.__name__ = cls.__name__
+        return Rec
+    for name in ('MinkowskiConvolution', 'MinkowskiGenerativeConvolutionTranspose', 'MinkowskiReLU', 'MinkowskiPruning'):
+        setattr(facade, name, recording(getattr(ME, name)))
+    saved = {k: sys.modules.get(k) for k in ('MinkowskiEngine', 'data_utils')}
+    sys.modules['MinkowskiEngine'], sys.modules['data_utils'] = facade, du
+    try:
+        spec = importlib.util.spec_from_file_location('_ref_autoencoder', os.path.join(REF, 'autoencoder.py'))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        channels = {'encoder': [1, 16, 32, 64, 32, 8], 'decoder': [8, 64, 32, 16]}
+        parts = {'encoder': mod.Encoder(channels=channels['encoder']), 'decoder': mod.Decoder(channels=channels['decoder'])}
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                sys.modules.pop(k, None)
+            else:
+                sys.modules[k] = v
+    layers, params = [], {}
+    for part, m in parts.items():
+        for name, sub in m.named_modules():
+            if hasattr(sub, 'golden_call'):
+                layers.append({'name': f'{part}.{name}', 'class': type(sub).__name__, 'args': sub.golden_call})
+        params.update({f'{part}.{k}': list(v.shape) for k, v in m.state_dict().items()})
+    with open(os.path.join(OUT, 'autoencoder_modules.json'), 'w') as f:          # (one layer / parameter per line)
+        f.write('{"channels": ' + json.dumps(channels) + ',\n"layers": [\n' + ',\n'.join(json.dumps(l) for l in layers) + '],\n"params": {\n'
+                + ',\n'.join(f'{json.dumps(k)}: {json.dumps(v)}' for k, v in params.items()) + '}}\n')
+
+
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['g1', 'g2', 'g3', 'g4', 'g6']
+    which = sys.argv[1:] or ['g1', 'g2', 'g3', 'g4', 'g6', 'g7']
     for name in which:
-        {'g1': g1, 'g2': g2, 'g3': g3, 'g4': g4, 'g6': g6}[name]()
+        {'g1': g1, 'g2': g2, 'g3': g3, 'g4': g4, 'g6': g6, 'g7': g7}[name]()
     print('golden fixtures written to', OUT)

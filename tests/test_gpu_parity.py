@@ -1399,6 +1399,26 @@ def test_bench_eight_ranks_blocks_dry_run_over_gloo():
     assert eight['config']['host_threads']['cpus'] >= 1 and eight['config']['host_threads']['rc_threads'] >= 1
 
 
+def test_bench_dump_outputs_are_deterministic(tmp_path):
+    """--steps K times exactly K steps; --dump-outputs DIR writes a decoded cloud and bitstream files as float .npy, and two runs with
+    the same arguments write the same files.  (Every step codes the same input, so this cannot tell the last timed step from another;
+    the byte cap's sampling is tested on the host, tests/test_host_cpu.py.)"""
+    dumps = []
+    for run in ('a', 'b'):
+        d = tmp_path / run
+        r, line = _run_bench(['--steps', '3', '--warmup', '0', '--workload', 'shell9', '--no-cpu-baseline', '--no-events', '--no-extra',
+                              '--dump-outputs', str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert line['steps'] == 3 and len(line['config']['step_ms_rank0']) == 3 and line['ms_per_step'] > 0
+        dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    a, b = dumps
+    assert sorted(a) == sorted(b) and {'out0_coords.npy', 'out0_feats.npy', 'shell9_F_bin.npy', 'shell9_C_bin.npy'} <= set(a)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 * 10 ** 6
+    assert a['out0_coords.npy'].shape == (line['config']['points_out'], 4)
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+
+
 def test_bench_refuses_a_world_size_mismatch():
     r, line = _run_bench(['--gpus', '2', '--steps', '1', '--warmup', '0'])
     assert r.returncode == 2 and line is None and 'WORLD_SIZE' in r.stderr
