@@ -377,6 +377,50 @@ int pcgc_d1_nn_cells(const int32_t* a /*[dev na,4]*/, int64_t na, const uint64_t
                      const uint64_t* masks, const int32_t* offsets /*[dev n,4]*/, int n_offsets, int32_t reach2, double* sum, uint64_t* max_d2,
                      int32_t* unresolved, void* stream);
 
+/* ---- D2 point-to-plane distortion (pc_error.py:27-74 with normal=True, as the reference's test.py:74-75 asks for it -> mpeg-pcc-dmetric ‡
+ *      with `-n infile1`; semantics of pc_error.d2_psnr, restated by oracle/pcgc_oracle.py:d2_metrics).  csrc/metric.hip.
+ *      A searched cloud Q is given by its rows sorted with pcgc_sort_bzyx (qs [nq,4], perm = original row of each sorted row), runlen
+ *      (pcgc_d2_runs), the coordinate hash of qs (keys / vals, stride 1: vals = first sorted row of a voxel) and the stride-4 cells of qs
+ *      (cell_keys / cell_vals / masks exactly as for pcgc_d1_nn_cells).  Tie sets are ORIGINAL rows of Q; all buffers caller-owned, on `stream`. */
+/* run length of the equal rows starting at each sorted row (0 where a run does not start) */
+int pcgc_d2_runs(const int32_t* qs /*[dev nq,4]*/, int64_t nq, int32_t* runlen /*[dev nq]*/, void* stream);
+/* per query point p[sel[t]] (sel = NULL: every point, n = rows of p): best = nearest squared distance, cnt = rows of Q at it (duplicates
+ * included).  The walk stops only at a bound ABOVE the best distance; a point whose best is not below reach2 (a nearer or tied row could lie
+ * outside the offset table) gets best = INT64_MAX, cnt = 0 and is appended to unresolved (n_unresolved is zeroed first). */
+int pcgc_d2_count(const int32_t* p /*[dev np,4]*/, int64_t n, const int32_t* sel, const uint64_t* cell_keys, const int32_t* cell_vals,
+                  int64_t cell_cap, const uint64_t* masks, const uint64_t* keys, const int32_t* vals, int64_t cap, const int32_t* runlen,
+                  const int32_t* offsets /*[dev n_offsets,4]*/, int n_offsets, int32_t reach2, int64_t* best /*[dev np]*/, int32_t* cnt /*[dev np]*/,
+                  int32_t* unresolved /*[dev n]*/, int32_t* n_unresolved /*[dev 1]*/, void* stream);
+/* the tie rows of every listed point whose best is below reach2 into rows[seg[i] .. seg[i+1]) (other points are left to another table) */
+int pcgc_d2_fill(const int32_t* p, int64_t n, const int32_t* sel, const uint64_t* cell_keys, const int32_t* cell_vals, int64_t cell_cap,
+                 const uint64_t* masks, const uint64_t* keys, const int32_t* vals, int64_t cap, const int32_t* runlen, const int32_t* perm,
+                 const int32_t* offsets, int n_offsets, int32_t reach2, const int64_t* best, const int64_t* seg /*[dev np+1]*/, int32_t* rows, void* stream);
+/* the exhaustive finish of listed points: every row of qs with the point's batch.  fill = 0: best / cnt (n_empty counts points whose batch
+ * has no row in Q); fill = 1: the tie rows into their segments. */
+int pcgc_d2_exhaustive(const int32_t* p, int64_t n, const int32_t* sel, const int32_t* qs, int64_t nq, const int32_t* perm, int fill,
+                       int64_t* best, int32_t* cnt, const int64_t* seg, int32_t* rows, int32_t* n_empty /*[dev 1]*/, void* stream);
+/* seg[0] = 0, seg[i+1] = cnt[0] + ... + cnt[i] (int64) */
+size_t pcgc_d2_scan_workspace_bytes(int64_t n);
+int pcgc_d2_scan(const int32_t* cnt /*[dev n]*/, int64_t n, int64_t* seg /*[dev n+1]*/, void* workspace, size_t workspace_bytes, void* stream);
+/* per segment: its `cap` lowest values in ascending order at its head; kept (optional) [n] = min(size, cap) */
+int pcgc_d2_segment_lowest(const int64_t* seg, int64_t n, int32_t* rows, int32_t cap, int32_t* kept, void* stream);
+/* the reverse relation of the kept A -> B tie sets: rcnt [nb] = A-points holding b (zeroed first); after pcgc_d2_scan(rcnt) -> rseg, recv holds
+ * the A rows of each b (cursor [nb] is scratch; order them with pcgc_d2_segment_lowest) */
+int pcgc_d2_recv_count(const int64_t* seg, const int32_t* kept, int64_t na, const int32_t* rows, int64_t nb, int32_t* rcnt, void* stream);
+int pcgc_d2_recv_fill(const int64_t* seg, const int32_t* kept, int64_t na, const int32_t* rows, int64_t nb, const int64_t* rseg, int32_t* cursor,
+                      int32_t* recv, void* stream);
+/* normals of B (scaleNormals): mean of the received normals of A summed in ascending A row in fp64, or, none received, the mean normal of
+ * b's kept B -> A tie set.  na, nb_out: double [n,3]. */
+int pcgc_d2_normals(const int64_t* rseg, const int32_t* recv, int64_t nb, const double* na, const int64_t* seg_ba, const int32_t* kept_ba,
+                    const int32_t* rows_ba, double* nb_out, void* stream);
+/* c2p [np] (double) = mean over p's kept tie set of ((p - q) . n_q)^2, q the original rows of Q [nq,4], nq normals double [nq,3] */
+int pcgc_d2_c2p(const int32_t* p, int64_t n, const int32_t* q, const double* nq, const int64_t* seg, const int32_t* kept, const int32_t* rows,
+                double* c2p, void* stream);
+/* c2c_sum_max [2] = (sum, max) of c2c [n] (int64), c2p_sum [1] = sum of c2p [n]: fixed summation order (a function of n only) */
+size_t pcgc_d2_reduce_workspace_bytes(void);
+int pcgc_d2_reduce(const int64_t* c2c, const double* c2p, int64_t n, int64_t* c2c_sum_max, double* c2p_sum, void* workspace, size_t workspace_bytes,
+                   void* stream);
+
 /* ---- ASCII PLY geometry I/O (data_utils.py:19-48: read_ply_ascii_geo / write_ply_ascii_geo), HOST.
  *      read: returns the number of data rows (call with xyz = NULL to size the buffer); same acceptance rule as the
  *      reference (a line is data iff all its ' '-separated tokens parse as floats); columns 0:3 truncated to int. ---- */

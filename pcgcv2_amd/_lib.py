@@ -86,6 +86,19 @@ SIGNATURES = {
     'pcgc_d1_cell_masks': (ci, [vp, i64, vp, vp, i64, vp, i64, vp]),
     'pcgc_d1_nn_cells': (ci, [vp, i64, vp, vp, i64, vp, vp, ci, i32, vp, vp, vp, vp]),
     'pcgc_d1_nn': (ci, [vp, i64, vp, vp, i64, vp, ci, vp, vp, vp, vp]),
+    'pcgc_d2_runs': (ci, [vp, i64, vp, vp]),
+    'pcgc_d2_count': (ci, [vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, ci, i32, vp, vp, vp, vp, vp]),
+    'pcgc_d2_fill': (ci, [vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, ci, i32, vp, vp, vp, vp]),
+    'pcgc_d2_exhaustive': (ci, [vp, i64, vp, vp, i64, vp, ci, vp, vp, vp, vp, vp, vp]),
+    'pcgc_d2_scan_workspace_bytes': (sz, [i64]),
+    'pcgc_d2_scan': (ci, [vp, i64, vp, vp, sz, vp]),
+    'pcgc_d2_segment_lowest': (ci, [vp, i64, vp, i32, vp, vp]),
+    'pcgc_d2_recv_count': (ci, [vp, vp, i64, vp, i64, vp, vp]),
+    'pcgc_d2_recv_fill': (ci, [vp, vp, i64, vp, i64, vp, vp, vp, vp]),
+    'pcgc_d2_normals': (ci, [vp, vp, i64, vp, vp, vp, vp, vp, vp]),
+    'pcgc_d2_c2p': (ci, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+    'pcgc_d2_reduce_workspace_bytes': (sz, []),
+    'pcgc_d2_reduce': (ci, [vp, vp, i64, vp, vp, vp, sz, vp]),
     'pcgc_rc_encode': (i64, [vp, ci, ci, vp, i64, vp, i64]),
     'pcgc_rc_decode': (ci, [vp, ci, ci, vp, i64, vp, i64]),
     'pcgc_set_rc_impl': (ci, [ci]),

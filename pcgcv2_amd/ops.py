@@ -1513,6 +1513,122 @@ def d1_nn(a, b, radius=12):
     return s, m, u
 
 
+# ------------------------------------------------------------------------------------------------ D2 metric (csrc/metric.hip)
+D2_TIES = 30                       # tie sets hold at most this many rows: the lowest original rows (mpeg-pcc-dmetric's k = 30 search)
+D2_REACH_CELLS = (4, 16)           # cell tables searched in turn (reach 17 and 65 voxels); what neither settles is searched exhaustively
+
+
+class D2Index:
+    """A cloud as the D2 search reads it: rows sorted by (batch, z, y, x) (stable: the duplicates of a voxel are one run in ascending
+    original row), run lengths, the voxel hash of the sorted rows and their stride-4 cells with occupancy masks."""
+
+    def __init__(self, q):
+        q = _i32(q)
+        n = q.shape[0]
+        self.coords, self.n = q, n
+        self.perm = sort_zyx(q, batch_major=True)
+        self.qs = torch.empty_like(q)
+        check(lib().pcgc_gather_rows_i32x4(_p(q), _p(self.perm), n, _p(self.qs), _stream(q)), 'gather_rows_i32x4')
+        self.runlen = torch.empty(n, dtype=torch.int32, device=q.device)
+        check(lib().pcgc_d2_runs(_p(self.qs), n, _p(self.runlen), _stream(q)), 'd2_runs')
+        self.voxels = HashTable(self.qs, 1)                 # voxel -> first sorted row of its run
+        self.cells = HashTable(coords_quantize(self.qs, 4), 4)
+        self.masks = torch.empty(n, dtype=torch.int64, device=q.device)
+        check(lib().pcgc_d1_cell_masks(_p(self.qs), n, _p(self.cells.keys), _p(self.cells.vals), self.cells.cap, _p(self.masks), n, _stream(q)),
+              'd1_cell_masks')
+
+    def tables(self):
+        return (_p(self.cells.keys), _p(self.cells.vals), self.cells.cap, _p(self.masks), _p(self.voxels.keys), _p(self.voxels.vals),
+                self.voxels.cap, _p(self.runlen))
+
+
+def _d2_scan(cnt):
+    n = cnt.shape[0]
+    seg = torch.empty(n + 1, dtype=torch.int64, device=cnt.device)
+    ws_bytes = int(lib().pcgc_d2_scan_workspace_bytes(n))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=cnt.device)
+    check(lib().pcgc_d2_scan(_p(cnt), n, _p(seg), _p(ws), ws_bytes, _stream(cnt)), 'd2_scan')
+    return seg
+
+
+def d2_nn(p, q):
+    """Nearest-distance tie sets of every point of p in q (q: a D2Index or an int32 [N,4] device tensor), exact at any distance.
+    -> (c2c int64 [Np] = nearest squared distance, seg int64 [Np+1], kept int32 [Np], rows int32): the tie set of point i is
+    rows[seg[i] : seg[i] + kept[i]], ascending ORIGINAL rows of q, at most D2_TIES of them (the lowest rows when more tie)."""
+    p = _i32(p, 'p')
+    q = q if isinstance(q, D2Index) else D2Index(q)
+    n, dev, st = p.shape[0], p.device, _stream(p)
+    best = torch.empty(n, dtype=torch.int64, device=dev)
+    cnt = torch.empty(n, dtype=torch.int32, device=dev)
+    n_out = torch.empty(1, dtype=torch.int32, device=dev)
+    stages = []                                             # (offset table, reach2, selection list or None, its length)
+    sel, n_sel = None, n
+    for reach_cells in D2_REACH_CELLS:
+        off = _d1_cell_offsets(dev, reach_cells)
+        reach = 4 * (reach_cells + 1) - 3
+        out = torch.empty(max(n_sel, 1), dtype=torch.int32, device=dev)
+        check(lib().pcgc_d2_count(_p(p), n_sel, _p(sel), *q.tables(), _p(off), off.shape[0], reach * reach, _p(best), _p(cnt), _p(out),
+                                  _p(n_out), st), 'd2_count')
+        stages.append((off, reach * reach, sel, n_sel))
+        sel, n_sel = out, int(n_out.item())
+        if n_sel == 0:
+            break
+    if n_sel:                                               # farther than every table reaches: every row of q with the point's batch
+        check(lib().pcgc_d2_exhaustive(_p(p), n_sel, _p(sel), _p(q.qs), q.n, _p(q.perm), 0, _p(best), _p(cnt), None, None, _p(n_out), st),
+              'd2_exhaustive')
+        if int(n_out.item()):
+            raise PcgcError(f'd2_nn: {int(n_out.item())} points have a batch index with no point in the other cloud')
+    seg = _d2_scan(cnt)
+    rows = torch.empty(max(int(seg[-1].item()), 1), dtype=torch.int32, device=dev)
+    for off, reach2, s, ns in stages:
+        check(lib().pcgc_d2_fill(_p(p), ns, _p(s), *q.tables(), _p(q.perm), _p(off), off.shape[0], reach2, _p(best), _p(seg),
+                                 _p(rows), st), 'd2_fill')
+    if n_sel:
+        check(lib().pcgc_d2_exhaustive(_p(p), n_sel, _p(sel), _p(q.qs), q.n, _p(q.perm), 1, _p(best), None, _p(seg), _p(rows), None, st),
+              'd2_exhaustive')
+    kept = torch.empty(n, dtype=torch.int32, device=dev)
+    check(lib().pcgc_d2_segment_lowest(_p(seg), n, _p(rows), D2_TIES, _p(kept), st), 'd2_segment_lowest')
+    return best, seg, kept, rows
+
+
+def d2_normals(nb, ab, na, ba):
+    """Normals of cloud B (nb rows) from those of A (na: float64 [Na,3] device): ab = d2_nn(A, B), ba = d2_nn(B, A).  -> float64 [nb,3]"""
+    _, seg, kept, rows = ab
+    _, seg_ba, kept_ba, rows_ba = ba
+    na = _dev(na, torch.float64, 'normals')
+    dev, st = na.device, _stream(na)
+    rcnt = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
+    check(lib().pcgc_d2_recv_count(_p(seg), _p(kept), kept.shape[0], _p(rows), nb, _p(rcnt), st), 'd2_recv_count')
+    rseg = _d2_scan(rcnt[:nb])
+    recv = torch.empty(max(int(rseg[-1].item()), 1), dtype=torch.int32, device=dev)
+    cursor = torch.empty(max(nb, 1), dtype=torch.int32, device=dev)
+    check(lib().pcgc_d2_recv_fill(_p(seg), _p(kept), kept.shape[0], _p(rows), nb, _p(rseg), _p(cursor), _p(recv), st), 'd2_recv_fill')
+    check(lib().pcgc_d2_segment_lowest(_p(rseg), nb, _p(recv), 0x7FFFFFFF, None, st), 'd2_segment_lowest')     # ascending A row
+    out = torch.empty((nb, 3), dtype=torch.float64, device=dev)
+    check(lib().pcgc_d2_normals(_p(rseg), _p(recv), nb, _p(na), _p(seg_ba), _p(kept_ba), _p(rows_ba), _p(out), st), 'd2_normals')
+    return out
+
+
+def d2_c2p(p, q, nq, nn):
+    """c2p float64 [Np] of p against q (int32 [Nq,4]) with q's normals nq (float64 [Nq,3]) over the tie sets nn = d2_nn(p, q)"""
+    _, seg, kept, rows = nn
+    out = torch.empty(p.shape[0], dtype=torch.float64, device=p.device)
+    check(lib().pcgc_d2_c2p(_p(_i32(p, 'p')), p.shape[0], _p(_i32(q, 'q')), _p(_dev(nq, torch.float64, 'normals')), _p(seg), _p(kept), _p(rows),
+                            _p(out), _stream(p)), 'd2_c2p')
+    return out
+
+
+def d2_reduce(c2c, c2p):
+    """-> (int64 [2] = sum and max of c2c, float64 [1] = sum of c2p), in a fixed order"""
+    n, dev = c2c.shape[0], c2c.device
+    sm = torch.empty(2, dtype=torch.int64, device=dev)
+    s = torch.empty(1, dtype=torch.float64, device=dev)
+    ws_bytes = int(lib().pcgc_d2_reduce_workspace_bytes())
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    check(lib().pcgc_d2_reduce(_p(c2c), _p(c2p), n, _p(sm), _p(s), _p(ws), ws_bytes, _stream(c2c)), 'd2_reduce')
+    return sm, s
+
+
 # ------------------------------------------------------------------------------------------------ host codecs (numpy)
 def _np(a, dt):
     return np.ascontiguousarray(a, dtype=dt)

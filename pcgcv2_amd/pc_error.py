@@ -29,6 +29,11 @@ def number_in_line(line):
     return number
 
 
+D1_COLUMNS = ['mse1      (p2point)', 'mse1,PSNR (p2point)', 'h.       1(p2point)', 'h.,PSNR  1(p2point)',
+              'mse2      (p2point)', 'mse2,PSNR (p2point)', 'h.       2(p2point)', 'h.,PSNR  2(p2point)',
+              'mseF      (p2point)', 'mseF,PSNR (p2point)', 'h.        (p2point)', 'h.,PSNR   (p2point)']     # what pc_error() reports for D1
+
+
 def d1_sums(a, b):
     """-> (sum of squared NN distances a->b, max) with an exact KD-tree search (scipy, host)."""
     from scipy.spatial import cKDTree
@@ -194,6 +199,58 @@ def d1_psnr_device(a, b, res, radius=12):
             'mseF      (p2point)': max(mse1, mse2), 'mseF,PSNR (p2point)': psnr(max(mse1, mse2)),
             'h.        (p2point)': max(h1, h2), 'h.,PSNR   (p2point)': psnr(max(h1, h2)),
             'sse1': s1, 'sse2': s2}
+
+
+def lattice_coords(xyz, device, batch=0):
+    """float [n,3] coordinates (as read_ply_ascii_with_normals returns them) -> int32 [n,4] (batch, x, y, z) device tensor.  The device
+    metrics work on the integer lattice: a non-integer coordinate raises instead of being rounded."""
+    import torch
+    xyz = np.asarray(xyz, dtype=np.float64)
+    if xyz.size and not np.array_equal(xyz, np.rint(xyz)):
+        bad = int(np.count_nonzero((xyz != np.rint(xyz)).any(1)))
+        raise ValueError(f'{bad} of {len(xyz)} points have non-integer coordinates: the device metric needs voxelised clouds')
+    out = np.empty((len(xyz), 4), np.int32)
+    out[:, 0] = batch
+    out[:, 1:] = xyz
+    return torch.from_numpy(out).to(device)
+
+
+def d2_psnr_device(a, na, b, res):
+    """The columns of d2_psnr, computed on the GPU: a, b int32 [N,4] (batch, x, y, z) device tensors (or sparse tensors' .C), na the normals of
+    a ([Na,3], float32 or float64, used as fp64).  Neighbours are searched within the same batch index only.
+    Every row is a point of its own (duplicated rows are counted and appear in tie sets).  Tie sets: every point of the other cloud at the
+    nearest squared distance, at most 30 — when more tie (e.g. 48 lattice points at d2 = 14) the 30 with the LOWEST row indices, as
+    oracle/pcgc_oracle.py:d2_metrics keeps them (the host d2_psnr's k = 30 KD-tree query keeps an unspecified subset in that case).  Exact at
+    any distance: points the cell tables cannot settle are searched again with a larger table, then exhaustively (ops.d2_nn).
+    p2point columns equal d2_psnr's exactly (integer distances); p2plane columns to rounding (sums of the same terms in another order)."""
+    import torch
+    from . import ops
+    a, b = (t.C if hasattr(t, 'C') else t for t in (a, b))
+    a, b = a.contiguous(), b.contiguous()
+    if a.shape[0] == 0 or b.shape[0] == 0:
+        raise ValueError('d2_psnr_device: empty point cloud')
+    if na.shape != (a.shape[0], 3):
+        raise ValueError(f'd2_psnr_device: normals {tuple(na.shape)} do not match {a.shape[0]} points')
+    ops.check_coords(a, 'd2_psnr_device: a'); ops.check_coords(b, 'd2_psnr_device: b')
+    na = torch.as_tensor(na).to(device=a.device, dtype=torch.float64).contiguous()
+    ia, ib = ops.D2Index(a), ops.D2Index(b)
+    ab, ba = ops.d2_nn(a, ib), ops.d2_nn(b, ia)
+    nb = ops.d2_normals(b.shape[0], ab, na, ba)
+    sums = []
+    for p, q, nq, nn in ((a, b, nb, ab), (b, a, na, ba)):
+        sm, s = ops.d2_reduce(nn[0], ops.d2_c2p(p, q, nq, nn))
+        sums.append((sm, s))
+    (sm1, p1), (sm2, p2) = [(sm.cpu().tolist(), float(s.item())) for sm, s in sums]
+    s1, h1, s2, h2 = float(sm1[0]), float(sm1[1]), float(sm2[0]), float(sm2[1])
+    mse1, mse2, pl1, pl2 = s1 / a.shape[0], s2 / b.shape[0], p1 / a.shape[0], p2 / b.shape[0]
+    peak = float(res - 1)
+    psnr = lambda m: float(10 * np.log10(3 * peak * peak / m)) if m > 0 else float('inf')
+    return {'mse1      (p2point)': mse1, 'mse1,PSNR (p2point)': psnr(mse1), 'h.       1(p2point)': h1, 'h.,PSNR  1(p2point)': psnr(h1),
+            'mse2      (p2point)': mse2, 'mse2,PSNR (p2point)': psnr(mse2), 'h.       2(p2point)': h2, 'h.,PSNR  2(p2point)': psnr(h2),
+            'mseF      (p2point)': max(mse1, mse2), 'mseF,PSNR (p2point)': psnr(max(mse1, mse2)),
+            'h.        (p2point)': max(h1, h2), 'h.,PSNR   (p2point)': psnr(max(h1, h2)),
+            'mse1      (p2plane)': pl1, 'mse1,PSNR (p2plane)': psnr(pl1), 'mse2      (p2plane)': pl2, 'mse2,PSNR (p2plane)': psnr(pl2),
+            'mseF      (p2plane)': max(pl1, pl2), 'mseF,PSNR (p2plane)': psnr(max(pl1, pl2))}
 
 
 def pc_error(infile1, infile2, res, normal=False, show=False):

@@ -5,7 +5,11 @@ column names; `sweep(...)` is the underlying generator.
 What differs in execution: the input tensor — and its optional down-scaled version — is built once, and because the
 encoder's geometry pyramid and kernel maps depend only on the coordinates they are built by the first rate and reused by
 all others (they are cached on the tensor's coordinate levels).  D2 (point-to-plane) columns need normals in the
-input PLY (as the reference's `pc_error(..., normal=True)` does) and are computed natively when no `pc_error_d` binary is installed.  Checkpoints may be paths or in-memory state dicts."""
+input PLY (as the reference's `pc_error(..., normal=True)` does) and are computed natively when no `pc_error_d` binary is installed.  Checkpoints may be paths or in-memory state dicts.
+
+metric='host' (the default) computes D1 / D2 like the reference: pc_error() on the input PLY and the decoded PLY.  metric='device' computes
+the same columns on the GPU (pc_error.d2_psnr_device, or d1_psnr_device for a cloud without normals): the input's raw rows and normals are
+read and uploaded once, the decoded cloud is taken from the decoder's tensor directly (its PLY is still written), no pc_error_d is run."""
 import os
 import time
 
@@ -15,7 +19,8 @@ import torch
 
 from .coder import Coder, stream_bits
 from .data_utils import load_sparse_tensor, scale_sparse_tensor, write_ply_ascii_geo
-from .pc_error import pc_error, ply_has_normals
+from .pc_error import (D1_COLUMNS, d1_psnr_device, d2_psnr_device, lattice_coords, pc_error, ply_has_normals,
+                       read_ply_ascii_with_normals)
 from .pcc_model import PCCModel
 
 device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
@@ -40,14 +45,20 @@ def _timed(fn):
     return out, round(time.time() - t0, 3)
 
 
-def sweep(filedir, ckpts, outdir, scaling_factor=1.0, rho=1.0, res=1024):
-    """Yield one single-row DataFrame per checkpoint (columns as in the reference's results/*.csv)."""
+def sweep(filedir, ckpts, outdir, scaling_factor=1.0, rho=1.0, res=1024, metric='host'):
+    """Yield one single-row DataFrame per checkpoint (columns as in the reference's results/*.csv).  metric: 'host' or 'device' (module doc)."""
+    if metric not in ('host', 'device'):
+        raise ValueError(f"metric must be 'host' or 'device', got {metric!r}")
     x = load_sparse_tensor(filedir, device)
     os.makedirs(outdir, exist_ok=True)
     prefix = os.path.join(outdir, os.path.split(filedir)[-1].split('.')[0])
     x_in = scale_sparse_tensor(x, factor=scaling_factor) if scaling_factor != 1 else x
     model = PCCModel().to(device)
     with_normals = ply_has_normals(filedir)       # (test.py:74-75 always asks for D2: its test clouds carry normals; a cloud without them gets D1 only)
+    if metric == 'device':                        # the file's rows as the host metric reads them (not the deduplicated x), uploaded once
+        a_xyz, a_nrm = read_ply_ascii_with_normals(filedir)
+        a_dev = lattice_coords(a_xyz, device)
+        na_dev = torch.from_numpy(a_nrm).to(device) if with_normals else None
     for rate, ckpt in enumerate(ckpts, start=1):
         model.load_state_dict(_state_dict(ckpt))
         coder = Coder(model=model, filename=prefix)
@@ -60,7 +71,12 @@ def sweep(filedir, ckpts, outdir, scaling_factor=1.0, rho=1.0, res=1024):
         bpps = (bits / len(x)).round(3)
         dec_ply = prefix + tag + '_dec.ply'
         write_ply_ascii_geo(dec_ply, x_dec.C.detach().cpu().numpy()[:, 1:])
-        row = pc_error(filedir, dec_ply, res=res, normal=with_normals, show=False)
+        if metric == 'device':
+            b_dev = x_dec.C.detach().contiguous()
+            m = d2_psnr_device(a_dev, na_dev, b_dev, res) if with_normals else d1_psnr_device(a_dev, b_dev, res)
+            row = pd.DataFrame([{k: m[k] for k in (m if with_normals else D1_COLUMNS)}])
+        else:
+            row = pc_error(filedir, dec_ply, res=res, normal=with_normals, show=False)
         row["num_points(input)"], row["num_points(output)"], row["resolution"] = len(x), len(x_dec), res
         row["bits"], row["bpp"] = sum(bits).round(3), sum(bpps).round(3)
         row["bpp(coords)"], row["bpp(feats)"] = bpps[0], bpps[1]
@@ -68,12 +84,12 @@ def sweep(filedir, ckpts, outdir, scaling_factor=1.0, rho=1.0, res=1024):
         yield row
 
 
-def test(filedir, ckptdir_list, outdir, resultdir, scaling_factor=1.0, rho=1.0, res=1024, verbose=True):
-    """Reference entry point (test.py:13): runs the sweep, rewrites `<resultdir>/<cloud>.csv` after every rate."""
+def test(filedir, ckptdir_list, outdir, resultdir, scaling_factor=1.0, rho=1.0, res=1024, verbose=True, metric='host'):
+    """Reference entry point (test.py:13): runs the sweep, rewrites `<resultdir>/<cloud>.csv` after every rate.  metric: 'host' | 'device'."""
     os.makedirs(resultdir, exist_ok=True)
     csv_name = os.path.join(resultdir, os.path.split(filedir)[-1].split('.')[0] + '.csv')
     rows, table = [], None
-    for rate, row in enumerate(sweep(filedir, ckptdir_list, outdir, scaling_factor, rho, res), start=1):
+    for rate, row in enumerate(sweep(filedir, ckptdir_list, outdir, scaling_factor, rho, res, metric), start=1):
         rows.append(row)
         table = pd.concat(rows, ignore_index=True)
         table.to_csv(csv_name, index=False)
@@ -107,8 +123,11 @@ def main(argv=None):
     parser.add_argument("--res", type=int, default=1024, help='resolution')
     parser.add_argument("--rho", type=float, default=1.0, help='the ratio of the number of output points to the number of input points')
     parser.add_argument("--ckpts", nargs='*', default=REFERENCE_CKPTS)
+    parser.add_argument("--metric", choices=('host', 'device'), default='host',
+                        help='where D1 / D2 are computed: host (pc_error on the PLY files, as the reference) or device (GPU)')
     args = parser.parse_args(argv)
-    table = test(args.filedir, args.ckpts, args.outdir, args.resultdir, scaling_factor=args.scaling_factor, rho=args.rho, res=args.res)
+    table = test(args.filedir, args.ckpts, args.outdir, args.resultdir, scaling_factor=args.scaling_factor, rho=args.rho, res=args.res,
+                 metric=args.metric)
     name = os.path.split(args.filedir)[-1][:-4]
     try:
         plot_rd(table, name, os.path.join(args.resultdir, name + '.jpg'))
