@@ -23,9 +23,14 @@ Multi-GPU: one process per GPU (torch.distributed, backend nccl = RCCL); frames 
 shard them with no data-path collective ("weak" scaling for `frame`: 1 frame per GPU per step); the only collective is the
 final all-reduce of scalars after the timed region.
 
-JSON line: the round contract plus `roofline` (dominant sparse-conv kernel: found by an untimed analysis step that brackets
-every sparse-conv launch with HIP events, then bracketed alone inside the timed region) and `cpu_baseline` (the CPU oracle
-timed on this host on the SAME workload, rank 0, N=1 only).
+JSON line: the round contract plus `roofline` (dominant sparse-conv kernel: found by untimed analysis steps that bracket
+every sparse-conv launch with HIP events, then bracketed alone inside the timed region).
+
+A plain run sets up, runs the analysis steps, warms up, times the K steps, writes `--dump-outputs` and prints the line.  `--full`
+then measures everything else before printing: the auxiliary timings under `config` (reference format only, warm tables, input
+order, other geometry, step windows, a two-CPU rank, units one by one, serving), the host coordinate coder alone and its rate on
+other clouds, D1 of the decoded cloud, and `cpu_baseline` (the CPU oracle timed on this host on the SAME workload, rank 0, N=1
+only).  Without `--full` those keys are null or absent; `--no-extra` / `--no-cpu-baseline` trim a `--full` run.
 """
 import argparse
 import json
@@ -51,11 +56,14 @@ def parse():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--config', default='frame', choices=['frame', 'batch4', 'sweep', 'blocks'])
     ap.add_argument('--workload', default='', help='override the synthetic cloud of the chosen config (e.g. shell9 for a quick run)')
+    ap.add_argument('--full', action='store_true', help='after the timed steps, also measure everything beside the headline: the auxiliary timings '
+                                                        '(reference format only, warm tables, input order, other geometry, step windows, two-CPU rank, '
+                                                        'one by one, serving), the host coordinate coder and its rate, D1 and the CPU baseline')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-sample', default='', help='cloud for the CPU oracle (default: the bench workload itself)')
     ap.add_argument('--no-events', action='store_true', help='do not bracket the dominant kernel with HIP events')
     ap.add_argument('--detail', default='', help='optional path for a per-kernel-shape JSON breakdown')
-    ap.add_argument('--no-extra', action='store_true', help='skip the auxiliary measurements after the timed region (reference-format-only / one-by-one / serving): profiler runs')
+    ap.add_argument('--no-extra', action='store_true', help='with --full: skip the auxiliary timings after the timed region (reference-format-only / one-by-one / serving)')
     ap.add_argument('--no-batch', action='store_true', help='blocks config: code the blocks one by one instead of as ONE collated batch')
     ap.add_argument('--serving-frames', type=int, default=16, help='frames of the extra serving-throughput measurement (0 = skip; frame config only)')
     ap.add_argument('--serving-in-flight', type=int, default=4, help='frames in flight per GPU in that measurement')
@@ -314,10 +322,14 @@ def main():
                                                        '(k3 / k1 convs, fused InceptionResNet passes, k2 s2 down convs, generative up convs)')
         roof['families'] = families
 
+    # A plain run measures nothing more: the auxiliary timings below, the host coordinate coder, D1 and the CPU baseline run with --full
+    # only.  The roofline above stays: it is sampled inside the timed steps, whose bracketed launches the analysis steps chose.
+    extra = args.full and not args.no_extra
+
     # the same K steps on the reference's four files alone (no `_F.idx` sidecar: the feature stream is decoded serially, exactly as a
     # reference-made stream would be) — reported beside `value`, so rate and speed of BOTH configurations are on the line
     plain = None
-    if cfg == 'frame' and not args.no_extra:
+    if cfg == 'frame' and extra:
         keep_segments, coder_mod.INDEX_SEGMENTS = coder_mod.INDEX_SEGMENTS, 0
         try:
             step()
@@ -345,7 +357,7 @@ def main():
 
     # the same K steps with the table caches left warm (what round 3 timed): reported beside the cold headline
     warm_tables = None
-    if not args.no_extra and cold['on']:
+    if extra and cold['on']:
         cold['on'] = False
         try:
             dt_p = timed_steps()
@@ -358,7 +370,7 @@ def main():
     # the headline cloud with its rows in the OTHER order: the canonical row order of every encoder level follows the input order
     # (a raster-ordered synthetic shell is the friendliest case for the gather kernels; a scanner's PLY has no particular order)
     order_sens = None
-    if cfg == 'frame' and not args.no_extra:
+    if cfg == 'frame' and extra:
         other = 'shuffled' if args.input_order == 'raster' else 'raster'
         name0 = units[0][0]
         alt = [(name0 + '_alt', cloud(name0, other))]
@@ -374,7 +386,7 @@ def main():
     # shells + one-voxel sheets + a rod + a solid block (multi10), a filled body with 27 / 27 neighbourhoods and whole regions of tied
     # logits (solid_ball); cold tables, the headline's warm-up
     geom_sens = None
-    if cfg == 'frame' and world == 1 and not args.no_extra and not args.two_cpu_child and not args.workload:
+    if cfg == 'frame' and world == 1 and extra and not args.two_cpu_child and not args.workload:
         geom_sens = {}
         for nm in ('noisy10', 'multi10', 'solid_ball'):
             alt = [(nm, cloud(nm))]
@@ -409,7 +421,7 @@ def main():
         return {'enc_gpu_window_ms': med(0), 'host_serial_ms': med(1), 'dec_gpu_window_ms': med(2)}
 
     windows = None
-    if cfg == 'frame' and not args.no_extra and batch is None and rate_sds is None:
+    if cfg == 'frame' and extra and batch is None and rate_sds is None:
         windows = step_windows()
         if windows:
             windows.update(gpu_conv_ms=None if warm_all is None else warm_all['ms_per_step'],
@@ -428,7 +440,7 @@ def main():
     # one rank on a TWO-CPU budget (eight ranks of a node that share a 16-CPU quota get exactly that): the same command in a child process
     # whose affinity mask holds two CPUs — configure_host_threads then budgets one range-decoder thread (the lane-parallel decoder), no pools
     two_cpu = None
-    if cfg == 'frame' and world == 1 and not args.no_extra and not args.two_cpu_child and hasattr(os, 'sched_setaffinity'):
+    if cfg == 'frame' and world == 1 and extra and not args.two_cpu_child and hasattr(os, 'sched_setaffinity'):
         import subprocess
         cpus = sorted(os.sched_getaffinity(0))[:2]
         if len(cpus) == 2:
@@ -451,7 +463,7 @@ def main():
                 two_cpu = {'error': str(e)[:200]}
 
     one_by_one = None
-    if batch is not None and not args.no_extra:
+    if batch is not None and extra:
         step(one_by_one=True)
         barrier()
         t_p = time.perf_counter()
@@ -464,7 +476,7 @@ def main():
         step()
 
     serving = None
-    if cfg == 'frame' and world == 1 and args.serving_frames > 0 and not args.no_extra:
+    if cfg == 'frame' and world == 1 and args.serving_frames > 0 and extra:
         # serving mode (reported beside the headline, never as `value`): independent frames collated into batches of F and coded by ONE
         # encoder / decoder pass per batch (Coder.encode_batch / decode_batch) — one frame's sequential host stages (range coder, octree
         # coder, files) run beside the other frames' on a thread pool inside the call, the small-level kernels work on F-times larger
@@ -501,7 +513,7 @@ def main():
                    'note': 'independent vox10 frames collated F at a time and coded by one encoder / decoder pass per batch (Coder.encode_batch / '
                            'decode_batch), best of 3 passes; the headline `value` is the single-frame-at-a-time rate'}
         del batches
-    elif cfg in ('batch4', 'blocks') and args.serving_in_flight > 1 and len(units) > 1 and batch is None:
+    elif cfg in ('batch4', 'blocks') and args.full and args.serving_in_flight > 1 and len(units) > 1 and batch is None:
         # the same units of this rank, several in flight (blocks / frames are independent; only the single-unit latency needs them one by one)
         for _, u in units:
             u.cmap.drop_caches()
@@ -522,7 +534,7 @@ def main():
     # the coordinate-coder stage on its own (report with and without it).  Inside a step it runs on a helper
     # thread concurrently with the GPU, so it adds nothing to ms_per_step unless it outlasts the work it hides behind.
     coord_ms = None
-    if units:
+    if units and args.full:
         from pcgcv2_amd import gpcc
         first = [f for f in sorted(os.listdir(tmp)) if f.endswith('_C.bin')][0]
         c8 = gpcc.native_decode(os.path.join(tmp, first))
@@ -534,7 +546,7 @@ def main():
     # `_C.bin` on geometry that is NOT the shape the octree coder's contexts were trained on (they are trained, once per process, on an
     # integer-defined sphere shell; every bench cloud is a sphere shell too: its 1.7 bit per stride-8 point is a best case)
     coord_rate = None
-    if cfg == 'frame' and world == 1 and not args.no_extra and not args.two_cpu_child:
+    if cfg == 'frame' and world == 1 and extra and not args.two_cpu_child:
         from pcgcv2_amd import gpcc
         from pcgcv2_amd.sparse import CoordMap
         coord_rate = {}
@@ -567,10 +579,10 @@ def main():
 
     # quality of this rank's first unit (outside the timed region, as coder.py:180-182): D1 on the GPU
     d1 = None
-    if units and cfg != 'blocks':
+    if args.full and units and cfg != 'blocks':
         from pcgcv2_amd.pc_error import d1_psnr_device
         d1 = d1_psnr_device(units[0][1].C, outs[0].C, {'shell11': 2048, 'shell12': 4096}.get(base, 1024))
-    elif cfg == 'blocks':
+    elif args.full and cfg == 'blocks':
         # exact GLOBAL D1 of the blocked cloud (SURVEY 8e caveat b: a per-block D1 misses nearest neighbours across block borders):
         # every rank's decoded blocks travel to rank 0 in one padded all-gather (shard.gather_varlen: RCCL over xGMI), are scaled back
         # (coder.py:166) and compared with the original cloud there
@@ -616,7 +628,7 @@ def main():
                        'coord_codec': 'native-octree (tmc3 absent)', 'coord_coder_ms': coord_ms, 'coord_codec_rate': coord_rate, 'serving_throughput': serving,
                        'step_ms_rank0': step_ms,
                        'd1_psnr_rank0_db': None if d1 is None else round(d1['mseF,PSNR (p2point)'], 4),
-                       'd1_scope': 'whole blocked cloud, decoded blocks gathered to rank 0 (shard.gather_varlen)' if cfg == 'blocks' else "this rank's first unit",
+                       'd1_scope': None if not args.full else 'whole blocked cloud, decoded blocks gathered to rank 0 (shard.gather_varlen)' if cfg == 'blocks' else "this rank's first unit",
                        'rccl_loaded': any('librccl' in l for l in open('/proc/self/maps')),
                        'collectives': ('RCCL' if backend == 'nccl' else backend) + (' (forced with one rank)' if dist_on and world == 1 else '') if dist_on else 'none (single process)',
                        'caveats': 'synthetic random weights: the decoder keeps the wrong voxels, so D1 only shows that the metric path runs, and bpp '
@@ -629,7 +641,7 @@ def main():
             order_sens[args.input_order] = round(value, 4) if world == 1 else None
         if roof is not None and cfg == 'frame' and not args.workload:      # (the PMC passes were collected on the frame workload)
             attach_pmc_traffic(roof)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(cfg, args.cpu_sample or base, sd)
         if args.detail and warm_detail is not None:
             with open(args.detail, 'w') as f:

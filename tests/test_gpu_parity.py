@@ -1369,9 +1369,9 @@ def test_bench_two_ranks_over_gloo_on_one_gpu():
 def test_bench_runs_its_collectives_over_rccl_with_one_rank():
     """No multi-GPU node is available to the builder, so the RCCL path runs with world_size 1 on this box's GPU: PCGC_DIST_FORCE=1
     makes bench.py create the `nccl` process group (RCCL communicator on the device), issue the barrier, both all-reduces and —
-    in the blocks configuration — the padded all-gather of decoded coordinates (shard.gather_varlen) that feeds the global D1.
+    in the blocks configuration with --full — the padded all-gather of decoded coordinates (shard.gather_varlen) that feeds the global D1.
     Done = the run succeeds, librccl is mapped into the process, and the reduced figures equal the single-process ones."""
-    args = ['--config', 'blocks', '--steps', '1', '--warmup', '1', '--workload', 'shell10', '--no-cpu-baseline', '--no-events']
+    args = ['--config', 'blocks', '--steps', '1', '--warmup', '1', '--workload', 'shell10', '--full', '--no-cpu-baseline', '--no-events']
     r, line = _run_bench(args, {'PCGC_DIST_FORCE': '1'})
     assert r.returncode == 0, r.stderr[-2000:]
     assert line['config']['collectives'].startswith('RCCL') and line['config']['rccl_loaded'] is True
@@ -1387,7 +1387,7 @@ def test_bench_eight_ranks_blocks_dry_run_over_gloo():
     global D1 (shard.gather_varlen: sizes, then a padded all-gather) — with the eight ranks sharing this box's one GPU and gloo carrying
     the collectives.  The reduced figures must equal the single-process run of the same blocks: same points in and out, same rate, the
     same global D1 (the nearest neighbours across block borders are found only if every rank's voxels arrive)."""
-    args = ['--config', 'blocks', '--steps', '1', '--warmup', '1', '--workload', 'shell10', '--no-cpu-baseline', '--no-events', '--no-extra']
+    args = ['--config', 'blocks', '--steps', '1', '--warmup', '1', '--workload', 'shell10', '--full', '--no-cpu-baseline', '--no-events', '--no-extra']
     r1, one = _run_bench(args)
     assert r1.returncode == 0, r1.stderr[-2000:]
     r8, eight = _run_bench(['--gpus', '8'] + args, {'PCGC_DIST_BACKEND': 'gloo'}, nproc=8, timeout=900)
@@ -1417,6 +1417,25 @@ def test_bench_dump_outputs_are_deterministic(tmp_path):
     assert a['out0_coords.npy'].shape == (line['config']['points_out'], 4)
     for k in a:
         np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+
+
+def test_bench_plain_run_leaves_the_rest_to_full():
+    """A plain run measures the headline and its roofline only; the auxiliary timings, the host coordinate coder, D1 and the CPU
+    baseline come with --full, whose line otherwise says what the plain one says."""
+    base = ['--steps', '2', '--warmup', '1', '--workload', 'shell9']
+    r, plain = _run_bench(base)
+    assert r.returncode == 0, r.stderr[-2000:]
+    r, full = _run_bench(base + ['--full', '--serving-frames', '4', '--serving-in-flight', '2', '--cpu-sample', 'shell7'])
+    assert r.returncode == 0, r.stderr[-2000:]
+    moved = ('reference_format_only', 'table_cache_warm', 'input_order_sensitivity', 'step_windows', 'two_cpu_rank', 'serving_throughput',
+             'coord_coder_ms', 'coord_codec_rate', 'd1_psnr_rank0_db', 'd1_scope')
+    assert 'cpu_baseline' not in plain and [k for k in moved if plain['config'][k] is not None] == []
+    assert full['cpu_baseline']['value'] > 0 and [k for k in moved if full['config'][k] is None] == []
+    assert plain['roofline'] is not None and full['roofline'] is not None
+    for k in ('metric', 'unit', 'higher_is_better', 'dtype', 'steps', 'warmup'):
+        assert plain[k] == full[k], k
+    for k in ('points_in_per_step_all_gpus', 'points_coded_per_step_all_gpus', 'points_out', 'bpp'):
+        assert plain['config'][k] == full['config'][k], k
 
 
 def test_bench_refuses_a_world_size_mismatch():

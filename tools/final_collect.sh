@@ -3,6 +3,7 @@ set -x
 # noisy10), SQ / TCC counters of the children-level and rows kernels, FETCH_SIZE calibration, and the bench lines of every config.  -> gpurun_out/final/
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out/final
+O=$_                                                  # the output directory just made
 timeout 600 bash $R/tools/pmc_traffic.sh > $R/gpurun_out/final/pmc.log 2>&1
 cp $R/profiles/pmc_traffic.json $R/gpurun_out/final/pmc_traffic.json
 cd /tmp && export TMPDIR=/tmp
@@ -27,8 +28,8 @@ bash tools/q4_pmc.sh shell10 > /dev/null 2>&1; cp gpurun_out/q4_pmc/summary.txt 
 for cfg in 16:irn 16:conv 32:irn; do
   bash tools/child_pmc.sh ${cfg%%:*} 0 0 ${cfg##*:} > /dev/null 2>&1; cp gpurun_out/child_pmc/summary.txt gpurun_out/final/child_pmc_${cfg%%:*}_${cfg##*:}.txt
 done
-python bench.py --steps 20 --warmup 5 --detail gpurun_out/final/detail.json > gpurun_out/final/bench_frame.json 2> gpurun_out/final/bench.err
-python bench.py --config batch4 --steps 5 --warmup 2 --no-cpu-baseline > gpurun_out/final/bench_batch4.json 2>> gpurun_out/final/bench.err
-python bench.py --config sweep --steps 2 --warmup 1 --no-cpu-baseline > gpurun_out/final/bench_sweep.json 2>> gpurun_out/final/bench.err
-python bench.py --config blocks --steps 3 --warmup 1 --no-cpu-baseline > gpurun_out/final/bench_blocks.json 2>> gpurun_out/final/bench.err
+python bench.py --full --steps 20 --warmup 5 --detail $O/detail.json > $O/bench_frame.json 2> $O/bench.err
+python bench.py --full --config batch4 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_batch4.json 2>> $O/bench.err
+python bench.py --full --config sweep --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_sweep.json 2>> $O/bench.err
+python bench.py --full --config blocks --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_blocks.json 2>> $O/bench.err
 tail -c 1200 gpurun_out/final/bench_frame.json

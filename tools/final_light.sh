@@ -12,10 +12,10 @@ python tools/trace_window_summary.py $O/kt_frame/*/*kernel_trace.csv 10 1 > $O/k
 python tools/rocprof_summary.py $O/kt_frame/*/*kernel_stats.csv > $O/kernel_stats_frame.txt 2>&1 || true
 python tools/trace_gaps.py $O/kt_frame/*/*kernel_trace.csv > $O/gpu_idle_gaps.txt 2>&1
 find $O/kt_frame -name '*kernel_trace.csv' -delete
-python bench.py --steps 20 --warmup 5 --detail $O/detail.json > $O/bench_frame.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 --detail $O/detail.json > $O/bench_frame.json 2> $O/bench.err
 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra > $O/bench_frame_again.json 2>> $O/bench.err
-python bench.py --config batch4 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_batch4.json 2>> $O/bench.err
-python bench.py --config sweep --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_sweep.json 2>> $O/bench.err
-python bench.py --config blocks --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_blocks.json 2>> $O/bench.err
+python bench.py --full --config batch4 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_batch4.json 2>> $O/bench.err
+python bench.py --full --config sweep --steps 2 --warmup 1 --no-cpu-baseline > $O/bench_sweep.json 2>> $O/bench.err
+python bench.py --full --config blocks --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_blocks.json 2>> $O/bench.err
 python bench.py --workload noisy10 --steps 20 --warmup 5 --no-cpu-baseline --no-extra > $O/bench_noisy10.json 2>> $O/bench.err
 tail -c 400 $O/bench_frame.json

@@ -19,11 +19,11 @@ PY
 }
 cd $R
 for cfg in frame batch4 sweep blocks; do
-    rocprofv3 --kernel-trace -d /tmp/zoo_$cfg -o t --output-format csv -- python bench.py --config $cfg --steps 2 --warmup 1 --no-extra --no-cpu-baseline > /tmp/zoo_$cfg.log 2>&1
+    rocprofv3 --kernel-trace -d /tmp/zoo_$cfg -o t --output-format csv -- python bench.py --config $cfg --steps 2 --warmup 1 --full --no-extra --no-cpu-baseline > /tmp/zoo_$cfg.log 2>&1
     names /tmp/zoo_$cfg > $O/bench_${cfg}_kernels.txt
     rm -rf /tmp/zoo_$cfg
 done
-rocprofv3 --kernel-trace -d /tmp/zoo_noisy -o t --output-format csv -- python bench.py --config frame --workload noisy10 --steps 2 --warmup 1 --no-extra --no-cpu-baseline > /tmp/zoo_noisy.log 2>&1
+rocprofv3 --kernel-trace -d /tmp/zoo_noisy -o t --output-format csv -- python bench.py --config frame --workload noisy10 --steps 2 --warmup 1 --full --no-extra --no-cpu-baseline > /tmp/zoo_noisy.log 2>&1
 names /tmp/zoo_noisy > $O/bench_noisy10_kernels.txt
 rm -rf /tmp/zoo_noisy
 rocprofv3 --kernel-trace -d /tmp/zoo_tests -o t --output-format csv -- python -m pytest tests -m gpu -q -x > $O/tests.log 2>&1
