@@ -319,6 +319,29 @@ int pcgc_cdf_table(const float* params /*[dev 352]*/, int C, float min_v, float 
                    float* cdf_f32 /*[dev] or NULL*/, void* stream);
 
 
+/* ---- forward losses of the training graph (loss.py:8-40; csrc/loss.hip).  None of this is on the encode/decode path.  Sums are reduced in
+ *      a fixed order without floating-point atomics (per-block fp64 partials in `workspace`, added by one block): bitwise reproducible.
+ *      workspace: pcgc_loss_workspace_bytes(elements) bytes, 8-byte aligned; elements = n * C (likelihood, bits) or n (BCE). ---- */
+size_t pcgc_loss_workspace_bytes(int64_t elements);
+/* data_utils.isin (data_utils.py:63-75): mask[i] = 1 iff row i of coords (batch, x, y, z) is a key of the table pcgc_hash_insert filled
+ * (cap = 0: the empty table), OR-ed with or_mask[i] when or_mask is given ("top-k | truth" of autoencoder.py:241-244 in one launch).
+ * Not pcgc_hash_first_mask, which marks the first occurrence of a row within its OWN table. */
+int pcgc_hash_contains(const int32_t* coords /*[dev n,4]*/, int64_t n, const uint64_t* keys, const int32_t* vals, int64_t cap,
+                       const uint8_t* or_mask /*[dev n] or NULL*/, uint8_t* mask /*[dev n]*/, void* stream);
+/* EntropyBottleneck._likelihood + Low_bound (entropy_model.py:112-140) at any real feats [n, C] (row stride ld): logits at v -+ 0.5, the
+ * sign trick, |sigmoid - sigmoid| evaluated in fp64 exactly as pcgc_cdf_table evaluates a table entry, rounded once to fp32, then
+ * max(., bound) (bound = 1e-9f in forward(); 0 = none).  likelihood [dev n,C] (may be NULL when only the bits are wanted);
+ * bits [dev 1] (may be NULL) = -sum log2(likelihood) over the stored fp32 values, in fp64 (loss.get_bits). */
+int pcgc_eb_likelihood(const float* feats, int ld, int64_t n, int C, const float* params /*[dev 44 C]*/, float bound, float* likelihood,
+                       double* bits, void* workspace, size_t workspace_bytes, void* stream);
+/* loss.get_bits of a likelihood tensor x [n, C] (row stride ld): -sum log2(x) in fp64; the same double pcgc_eb_likelihood returns for it */
+int pcgc_neg_log2_sum(const float* x, int ld, int64_t n, int C, double* bits /*[dev 1]*/, void* workspace, size_t workspace_bytes, void* stream);
+/* loss.get_bce + the counts of loss.get_cls_metrics in one pass: bce [dev 1] = sum_i (max(x,0) - x y + log1p(exp(-|x|))) / ln 2 over
+ * logits x [n] (row stride ld; NULL: counts only, bce = 0) and the truth mask y; counts [dev 4] = TP, FN, FP, TN of (pred, truth)
+ * (pred = NULL counts as all zero). */
+int pcgc_bce_logits(const float* logits, int64_t ld, int64_t n, const uint8_t* truth /*[dev n]*/, const uint8_t* pred /*[dev n] or NULL*/,
+                    double* bce, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- range coder, bit-compatible with torchac 0.9.3 ‡ encode_float_cdf / decode_float_cdf
  *      (entropy_model.py:174,192).  HOST functions; symbols row-major [point, channel], one CDF row per channel. ---- */
 int64_t pcgc_rc_encode(const uint16_t* cdf /*[host C,Lp]*/, int C, int Lp, const int16_t* sym /*[host n]*/, int64_t n,

@@ -6,8 +6,10 @@ goes through this module.  It exists so that code written against ME — the ref
 `ME.MinkowskiPruning()(data, mask)`), `data_utils.py` (`ME.SparseTensor(...)`, `ME.utils.sparse_collate`) — binds to the operators
 unmodified.  Same results as the fused graph, bit for bit (tests/test_gpu_parity.py::test_me_facade_unfused_graph_equals_fused).
 
-Not provided (outside the encode/decode path): coordinate_manager / coordinate_map_key plumbing of the
-training graph (pcc_model.py:18-23), MinkowskiEngine's other layers."""
+`ME.SparseTensor(features=, coordinate_map_key=, coordinate_manager=)` (pcc_model.py:18-23: a tensor that shares another's coordinates)
+binds too: the key of a tensor is its coordinate level (sparse.CoordMap) and the manager a token that only has to be handed back.
+
+Not provided: MinkowskiEngine's other layers, and anything with a backward."""
 import torch
 
 from . import ops
@@ -18,8 +20,37 @@ from .sparse import SparseTensor as _SparseTensor, sparse_collate as _sparse_col
 __version__ = '0.5.4-pcgcv2_amd'
 
 
+class _CoordinateManager:
+    def __repr__(self):
+        return 'CoordinateManager(pcgcv2_amd: the levels own their maps)'
+
+
+COORDINATE_MANAGER = _CoordinateManager()
+
+
 class SparseTensor(_SparseTensor):
     """ME.SparseTensor(features=, coordinates=, tensor_stride=, device=) plus the two operators autoencoder.py:55 applies to it."""
+
+    def __init__(self, features, coordinates=None, tensor_stride=1, device=None, coordinate_map=None, assume_unique=False,
+                 coordinate_map_key=None, coordinate_manager=None):
+        if coordinate_map_key is not None:                       # share the coordinates of the tensor the key was taken from
+            if coordinates is not None or coordinate_map is not None:
+                raise ValueError('ME.SparseTensor: give coordinates or a coordinate_map_key, not both')
+            if coordinate_manager is not None and coordinate_manager is not COORDINATE_MANAGER:
+                raise ValueError('ME.SparseTensor: foreign coordinate_manager')
+            coordinate_map = coordinate_map_key
+        super().__init__(features, coordinates=coordinates, tensor_stride=tensor_stride, device=device, coordinate_map=coordinate_map,
+                         assume_unique=assume_unique)
+
+    @property
+    def coordinate_map_key(self):
+        """the tensor's coordinate level: what ME calls a coordinate-map key (pcc_model.py:20)"""
+        return self.cmap
+
+    @property
+    def coordinate_manager(self):
+        """ME keeps every level in one manager object; here each level owns its tables, so the manager is a token (pcc_model.py:21)"""
+        return COORDINATE_MANAGER
 
     def __add__(self, other):
         if len(self) != len(other) or self.cmap is not other.cmap and not torch.equal(self.C, other.C):

@@ -83,6 +83,11 @@ SIGNATURES = {
     'pcgc_desymbolize': (ci, [vp, i64, f32, vp, vp]),
     'pcgc_quantize_symbols': (ci, [vp, i64, vp, vp, vp]),
     'pcgc_cdf_table': (ci, [vp, ci, f32, f32, vp, vp, vp]),
+    'pcgc_loss_workspace_bytes': (sz, [i64]),
+    'pcgc_hash_contains': (ci, [vp, i64, vp, vp, i64, vp, vp, vp]),
+    'pcgc_eb_likelihood': (ci, [vp, ci, i64, ci, vp, f32, vp, vp, vp, sz, vp]),
+    'pcgc_neg_log2_sum': (ci, [vp, ci, i64, ci, vp, vp, sz, vp]),
+    'pcgc_bce_logits': (ci, [vp, i64, i64, vp, vp, vp, vp, vp, sz, vp]),
     'pcgc_d1_cell_masks': (ci, [vp, i64, vp, vp, i64, vp, i64, vp]),
     'pcgc_d1_nn_cells': (ci, [vp, i64, vp, vp, i64, vp, vp, ci, i32, vp, vp, vp, vp]),
     'pcgc_d1_nn': (ci, [vp, i64, vp, vp, i64, vp, ci, vp, vp, vp, vp]),

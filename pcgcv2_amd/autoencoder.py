@@ -91,7 +91,8 @@ class Encoder(torch.nn.Module):
 
 
 class Decoder(torch.nn.Module):
-    """autoencoder.py:150-273 (inference: training=False, ground truth unused)."""
+    """autoencoder.py:150-273.  training=False: top-k pruning, ground truth unused (the codec).  training=True: top-k | ground truth
+    (teacher forcing), forward values only."""
 
     def __init__(self, channels=[8, 64, 32, 16]):
         super().__init__()
@@ -107,7 +108,7 @@ class Decoder(torch.nn.Module):
         """autoencoder.py:239-249 with istopk (data_utils.py:77-89) on device: per batch item b the nums[b] largest logits among
         the item's own rows (contiguous segments, sparse.CoordMap.batch_rows)."""
         if training:
-            raise NotImplementedError('training-time pruning (top-k ∪ ground truth) is outside the encode/decode path')
+            return self._prune_voxel_training(data, data_cls, nums, ground_truth)
         cand = data.cmap
         rows = [len(data_cls)] if len(nums) == 1 else cand.batch_rows
         if len(rows) != len(nums):
@@ -132,6 +133,22 @@ class Decoder(torch.nn.Module):
         out = SparseTensor(lambda: ops.gather_rows(src, orig), coordinate_map=cmap)
         out._F_rows = (src, orig)
         return out
+
+    def _prune_voxel_training(self, data, data_cls, nums, ground_truth):
+        """autoencoder.py:241-244: mask = top-k | isin(candidates, ground truth) — every true voxel survives, whatever the weights — through
+        the general-mask MinkowskiPruning path.  The membership probe reads the candidates' coordinates, so a children level that never
+        materialised them does so here.  Forward values only (no autograd)."""
+        if ground_truth is None:
+            raise ValueError('prune_voxel(training=True) needs the ground truth of the level')
+        from .data_utils import isin_mask
+        cand = data.cmap
+        rows = [len(data_cls)] if len(nums) == 1 else cand.batch_rows
+        if len(rows) != len(nums):
+            raise ValueError(f'prune_voxel: {len(nums)} budgets for a batch of {len(rows)} items')
+        keep = [int(min(r, max(int(n), 0))) for r, n in zip(rows, nums)]
+        topk = ops.topk_mask(data_cls.F, keep[0]) if len(nums) == 1 else ops.topk_mask_segments(data_cls.F, rows, keep)
+        mask = isin_mask(cand.C, ground_truth, or_mask=topk)
+        return self.pruning(data, mask)
 
     def forward(self, x, nums_list, ground_truth_list=(None, None, None), training=False):
         out, cls_list = x, []

@@ -38,12 +38,43 @@ def array2vector(array, step):
     return sum(array[:, i] * (step ** i) for i in range(array.shape[-1]))
 
 
+def _coords_of(t):
+    """(coordinate tensor, the level it belongs to or None) of a tensor / SparseTensor / CoordMap"""
+    if isinstance(t, SparseTensor):
+        return t.C, t.cmap
+    if isinstance(t, CoordMap):
+        return t.C, t
+    return torch.as_tensor(t), None
+
+
+def isin_mask(data, ground_truth, or_mask=None):
+    """isin on device as the uint8 mask the pruning and loss kernels read (pcgc_hash_contains), OR-ed with `or_mask` in the same launch.
+    `ground_truth` given as a SparseTensor / CoordMap is probed through the level's own (cached) hash table; a bare [M, 4] tensor gets a
+    table of its own."""
+    a, _ = _coords_of(data)
+    b, level = _coords_of(ground_truth)
+    a = a.to(torch.int32).contiguous()
+    if a.dim() != 2 or a.shape[1] != 4 or b.dim() != 2 or b.shape[1] != 4:
+        raise ValueError('isin on device expects [N, 4] coordinates (batch, x, y, z)')
+    if level is not None:
+        table = level.table if len(level) else None
+    else:
+        b = b.to(device=a.device, dtype=torch.int32).contiguous()
+        if b.shape[0]:
+            ops.check_coords(b, 'isin: ground truth')          # (a row the key cannot hold would silently never match)
+        table = ops.HashTable(b, 1) if b.shape[0] else None
+    return ops.hash_contains(a, table, or_mask=or_mask)
+
+
 def isin(data, ground_truth):
-    """data_utils.py:63-75: boolean vector, True where a row of `data` (int coordinates [N, D]) occurs in `ground_truth`.  Training-time
-    helper of the reference's Decoder.prune_voxel (autoencoder.py:241-243); provided so that `from data_utils import isin, istopk`
-    binds — host implementation, as in the reference."""
-    dev = data.device
-    a, b = torch.as_tensor(data).long().cpu(), torch.as_tensor(ground_truth).long().cpu()
+    """data_utils.py:63-75: boolean vector, True where a row of `data` (int coordinates [N, D]) occurs in `ground_truth`: the reference's
+    Decoder.prune_voxel (autoencoder.py:241-243) and loss.py use it.  Rows on the GPU are looked up in the ground truth's coordinate hash
+    (isin_mask; pass the SparseTensor instead of its `.C` to re-use the level's table); CPU tensors take the reference's host route."""
+    a, _ = _coords_of(data)
+    if a.is_cuda:
+        return isin_mask(data, ground_truth).bool()
+    dev = a.device
+    a, b = a.long().cpu(), _coords_of(ground_truth)[0].long().cpu()
     step = int(max(a.max(), b.max())) + 1
     return torch.isin(array2vector(a, step), array2vector(b, step)).to(dev)
 

@@ -1,4 +1,5 @@
-"""Factorized entropy bottleneck (reference entropy_model.py:42-196), inference path only.
+"""Factorized entropy bottleneck (reference entropy_model.py:42-196): compress / decompress and the forward pass (quantise + likelihood,
+no autograd).
 
 Same parameter names as the reference — `_matrices.{0..3}`, `_biases.{0..3}`, `_factors.{0..3}` and the three aliases
 `matrix` / `bias` / `factor` that the reference creates by assigning `self.matrix = Parameter(...)` inside its
@@ -223,6 +224,42 @@ class EntropyBottleneck(nn.Module):
                         cache.pop(next(iter(cache)), None)                       # (dicts keep insertion order: drop the oldest)
                     cache[key] = hit
         return hit if want_crc else hit[0]
+
+    def _quantize(self, inputs, mode, generator=None):
+        """entropy_model.py:103-110.  "noise": + uniform [-0.5, 0.5) drawn on the device (`generator`: a torch.Generator of that device, for
+        reproducible draws; the reference draws with numpy on the host); "symbols": round half to even."""
+        if mode == 'noise':
+            noise = torch.rand(inputs.shape, dtype=torch.float32, device=inputs.device, generator=generator) - 0.5
+            out = inputs + noise
+            # fp32 rounding of the sum can land on (or a hair beyond) an end of the interval: step such an element one float back inside
+            d = out.double() - inputs.double()
+            out = torch.where(d >= 0.5, torch.nextafter(out, torch.full_like(out, -float('inf'))), out)
+            return torch.where(d < -0.5, torch.nextafter(out, torch.full_like(out, float('inf'))), out)
+        if mode == 'symbols':
+            return torch.round(inputs)
+        raise PcgcError(f'quantize mode must be "noise", "symbols" or None, got {mode!r}')
+
+    def _check_inputs(self, inputs):
+        if inputs.dim() != 2 or inputs.shape[1] != self._channels:
+            raise PcgcError(f'the bottleneck expects [N, {self._channels}] features')
+        if not inputs.is_cuda or inputs.dtype != torch.float32:
+            raise PcgcError(f'the bottleneck runs on fp32 ROCm device tensors; got {inputs.dtype} on {inputs.device}')
+
+    @torch.no_grad()
+    def _likelihood(self, inputs):
+        """entropy_model.py:112-130 at any real inputs [points, channels] -> fp32 likelihood of the same shape (pcgc_eb_likelihood: fp64
+        evaluation of the fp32 parameters, one rounding).  No autograd graph is recorded."""
+        self._check_inputs(inputs)
+        return ops.eb_likelihood(inputs, self.packed_params(inputs.device), bound=0.0)[0]
+
+    @torch.no_grad()
+    def forward(self, inputs, quantize_mode='noise', generator=None):
+        """entropy_model.py:132-140 -> (outputs, likelihood), likelihood bounded below by 1e-9.  Forward values only: runs under
+        torch.no_grad(), nothing here has a backward."""
+        self._check_inputs(inputs)
+        outputs = inputs if quantize_mode is None else self._quantize(inputs, quantize_mode, generator=generator)
+        likelihood = ops.eb_likelihood(outputs, self.packed_params(inputs.device), bound=self._likelihood_bound)[0]
+        return outputs, likelihood
 
     @torch.no_grad()
     def compress(self, inputs, checkpoints=0, info=None):

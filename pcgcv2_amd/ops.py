@@ -1450,6 +1450,68 @@ def cdf_table(params, C, min_v, max_v):
     return q, f
 
 
+# ------------------------------------------------------------------------------------------------ forward losses (csrc/loss.hip)
+def _loss_ws(elements, device):
+    nbytes = int(lib().pcgc_loss_workspace_bytes(int(elements)))
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device), nbytes
+
+
+def hash_contains(coords, table, or_mask=None):
+    """data_utils.isin on device: uint8 [n], 1 where row i of coords [n, 4] (batch, x, y, z) is a key of `table` (a HashTable, or None for
+    the empty set), OR-ed with the uint8 mask `or_mask` when given."""
+    n = coords.shape[0]
+    mask = torch.empty(n, dtype=torch.uint8, device=coords.device)
+    if or_mask is not None and (_dev(or_mask, torch.uint8, 'or_mask').shape[0] != n):
+        raise PcgcError('hash_contains: or_mask length differs from the number of rows')
+    keys, vals, cap = (None, None, 0) if table is None else (table.keys, table.vals, table.cap)
+    check(lib().pcgc_hash_contains(_p(_i32(coords)), n, _p(keys), _p(vals), cap, _p(or_mask), _p(mask), _stream(coords)), 'hash_contains')
+    return mask
+
+
+def eb_likelihood(feats, params, bound=1e-9, want_likelihood=True, want_bits=False):
+    """EntropyBottleneck._likelihood (+ the lower bound, 0 = none) at feats [n, C] -> likelihood fp32 [n, C] and / or bits float64 [1]
+    = -sum log2(likelihood); (likelihood, bits) with None for what was not asked for."""
+    _f32(feats, 'feats')
+    n, C, ld = feats.shape[0], feats.shape[1], _ld(feats)
+    dev = feats.device
+    lik = torch.empty((n, C), dtype=torch.float32, device=dev) if want_likelihood else None
+    bits = torch.empty(1, dtype=torch.float64, device=dev) if want_bits else None
+    ws, ws_bytes = _loss_ws(n * C, dev) if want_bits else (None, 0)
+    check(lib().pcgc_eb_likelihood(_p(feats), ld, n, C, _p(_f32(params, 'params')), float(bound), _p(lik), _p(bits), _p(ws), ws_bytes,
+                                   _stream(feats)), 'eb_likelihood')
+    return lik, bits
+
+
+def neg_log2_sum(x):
+    """-sum log2(x) of an fp32 [n, C] view, in fp64 and in a fixed order -> float64 [1]"""
+    _f32(x, 'likelihood')
+    n, C, ld = x.shape[0], x.shape[1], _ld(x)
+    bits = torch.empty(1, dtype=torch.float64, device=x.device)
+    ws, ws_bytes = _loss_ws(n * C, x.device)
+    check(lib().pcgc_neg_log2_sum(_p(x), ld, n, C, _p(bits), _p(ws), ws_bytes, _stream(x)), 'neg_log2_sum')
+    return bits
+
+
+def bce_logits(logits, truth, pred=None):
+    """One pass over logits ([n] or [n, 1] fp32 view, or None), the uint8 truth mask and an optional uint8 prediction mask
+    -> (bce float64 [1] = sum of the BCE-with-logits terms / ln 2, counts int64 [4] = TP, FN, FP, TN)."""
+    n, dev = truth.shape[0], truth.device
+    _dev(truth, torch.uint8, 'truth')
+    if pred is not None and _dev(pred, torch.uint8, 'pred').shape[0] != n:
+        raise PcgcError('bce_logits: masks of different lengths')
+    ld = 1
+    if logits is not None:
+        _f32(logits, 'logits')
+        if logits.shape[0] != n or logits.dim() > 2 or (logits.dim() == 2 and logits.shape[1] != 1):
+            raise PcgcError(f'bce_logits: logits {tuple(logits.shape)} against a mask of {n} rows')
+        ld = max(int(logits.stride(0)), 1)
+    bce = torch.empty(1, dtype=torch.float64, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    ws, ws_bytes = _loss_ws((n + 3) // 4, dev)
+    check(lib().pcgc_bce_logits(_p(logits), ld, n, _p(truth), _p(pred), _p(bce), _p(counts), _p(ws), ws_bytes, _stream(truth)), 'bce_logits')
+    return bce, counts
+
+
 # ------------------------------------------------------------------------------------------------ D1 metric
 _D1_OFFSETS = {}
 

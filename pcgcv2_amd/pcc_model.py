@@ -1,10 +1,12 @@
 """PCCModel (reference pcc_model.py:8-45): container wiring Encoder [1,16,32,64,32,8], Decoder [8,64,32,16] and
-EntropyBottleneck(8).  Only the inference surface is on the encode/decode path; `forward` / `get_likelihood` are
-training-only in the reference and are not provided."""
+EntropyBottleneck(8).  coder.Coder drives the encode/decode path; `forward` / `get_likelihood` are the forward half of the
+reference's training graph (rate estimate, per-scale logits, teacher-forced pruning).  They run under torch.no_grad(): no backward
+kernels exist."""
 import torch
 
 from .autoencoder import Encoder, Decoder
 from .entropy_model import EntropyBottleneck
+from .sparse import SparseTensor
 
 
 class PCCModel(torch.nn.Module):
@@ -19,8 +21,28 @@ class PCCModel(torch.nn.Module):
         self.entropy_bottleneck.invalidate()
         return super().load_state_dict(conventions.permute_state_dict(state_dict), strict=strict, **kw)
 
-    def forward(self, x, training=True):
-        raise NotImplementedError('PCCModel.forward is the training graph (pcc_model.py:26-45); use coder.Coder for encode/decode')
+    @torch.no_grad()
+    def get_likelihood(self, data, quantize_mode, generator=None):
+        """pcc_model.py:15-24 -> (the quantised latent on data's coordinate level, likelihood [N, 8])."""
+        data_F, likelihood = self.entropy_bottleneck(data.F, quantize_mode=quantize_mode, generator=generator)
+        return SparseTensor(data_F, coordinate_map=data.cmap), likelihood
+
+    @torch.no_grad()
+    def forward(self, x, training=True, generator=None):
+        """pcc_model.py:26-45.  training=True: uniform noise on the latent (`generator`: optional torch.Generator on x's device) and
+        top-k | ground-truth pruning in the decoder; training=False: rounding and top-k pruning, i.e. what encode + decode compute.
+        Forward values only — under torch.no_grad(), nothing can be back-propagated."""
+        y_list = self.encoder(x)
+        y = y_list[0]
+        ground_truth_list = y_list[1:] + [x]
+        nums_list = [list(gt.cmap.batch_rows) for gt in ground_truth_list]
+        y_q, likelihood = self.get_likelihood(y, quantize_mode='noise' if training else 'symbols', generator=generator)
+        out_cls_list, out = self.decoder(y_q, nums_list, ground_truth_list, training)
+        return {'out': out,
+                'out_cls_list': out_cls_list,
+                'prior': y_q,
+                'likelihood': likelihood,
+                'ground_truth_list': ground_truth_list}
 
 
 if __name__ == '__main__':
