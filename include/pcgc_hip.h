@@ -76,6 +76,8 @@ int pcgc_mask_scan_zeroed(const uint8_t* mask, int64_t n, int32_t* prefix, int32
                           void* stream);
 int pcgc_compact_coords(const int32_t* coords, const uint8_t* mask, const int32_t* prefix, int64_t n,
                         int32_t* out /*[dev total,4]*/, void* stream);
+/* any C, in_ld >= C and any 4-byte aligned `in` / `out` (a column slice of a wider buffer): 16-byte accesses are used only when C and
+ * in_ld are multiples of 4 AND both bases are 16-byte aligned, a scalar kernel otherwise. */
 int pcgc_compact_feats(const float* in, int C, int in_ld, const uint8_t* mask, const int32_t* prefix, int64_t n,
                        float* out /*[dev total,C]*/, void* stream);
 
@@ -308,7 +310,10 @@ int pcgc_symbolize(const float* feats, int64_t count, float min_v, int16_t* sym 
 int pcgc_desymbolize(const int16_t* sym, int64_t count, float min_v, float* feats, void* stream);
 /* the two calls above with the symbol range kept on the device: minmax[2] <- (min, max), sym <- int16(round(feats) - min).
  * The host fetches both with one copy and evaluates the CDF table itself (reference arithmetic, see
- * pcgcv2_amd/entropy_model.py:reference_table). */
+ * pcgcv2_amd/entropy_model.py:reference_table).
+ * The symbols are only meaningful for a finite range of fewer than 32768 values (max - min + 1 < 32768: the int16 limit the reference
+ * shares, entropy_model.py:151-176).  The kernels do not check it: a NaN / infinite latent shows as a non-finite min or max (NaN orders
+ * beyond the infinity of its sign), and the CALLER must test the returned range before it uses the symbols (ops.quantize_symbols does). */
 int pcgc_quantize_symbols(const float* feats, int64_t count, float* minmax /*[dev 2]*/, int16_t* sym /*[dev count]*/, void* stream);
 /* per batch item (its own header range, coder.py:51-55): minmax [dev nseg,2], seg_rows [host nseg] rows of C channels each. */
 int pcgc_quantize_symbols_segments(const float* feats, int C, int nseg, const int64_t* seg_rows, float* minmax, int16_t* sym, void* stream);

@@ -291,7 +291,11 @@ class Coder():
             # (ops.table_warm: a dummy range, result discarded — the real table is evaluated below, once the range is known)
             if WARM_TABLE_CODE:
                 ops.table_warm(self.feature_coder.entropy_model._host_packed(), self.feature_coder.entropy_model._channels)
-            min_v, max_v, sym_h = ops.quantize_symbols(y.F)
+            try:
+                min_v, max_v, sym_h = ops.quantize_symbols(y.F)
+            except ops.PcgcError:
+                coded.result()                                  # (a latent int16 symbols cannot code: the coordinate coder finishes before the error leaves)
+                raise
             if TIMELINE is not None:
                 TIMELINE.append(('enc_gpu_done', time.perf_counter()))      # the symbols are on the host: nothing is queued on the GPU from here on
             ops.items_encode([self.filename + postfix], sym_h, np.zeros((0, 3), np.int32), [len(sym_h)], [(min_v, max_v)], [budgets],

@@ -151,7 +151,9 @@ extern "C" int pcgc_compact_coords(const int32_t* coords, const uint8_t* mask, c
 extern "C" int pcgc_compact_feats(const float* in, int C, int in_ld, const uint8_t* mask, const int32_t* prefix, int64_t n,
                                   float* out, void* stream) {
     if (n == 0) return 0;
-    if (C % 4 == 0 && in_ld % 4 == 0)
+    // 16-byte loads and stores need a 16-byte aligned base besides C and in_ld in whole float4s: a column slice that starts at an odd
+    // column pair (or any other misaligned view) takes the scalar kernel, like the vector loads of k_topk_select and k_round_minmax
+    if (C % 4 == 0 && in_ld % 4 == 0 && (((uintptr_t)in | (uintptr_t)out) & 15) == 0)
         hipLaunchKernelGGL(k_compact_feats4, dim3(grid_for(n * (C / 4), 256)), dim3(256), 0, S(stream), in, C / 4, in_ld, mask,
                            prefix, n, out);
     else

@@ -277,6 +277,7 @@ class EntropyBottleneck(nn.Module):
     def compress_symbols(self, sym_h, min_v, max_v, checkpoints=0, info=None, device=None):
         """The host half of compress(): int16 symbols [N, C] (= round(x) - min_v) + their range -> the same tuple compress returns.
         Thread-safe: the items of a batch are range-coded side by side (coder.Coder.encode_batch)."""
+        ops.check_symbol_range(min_v, max_v, 'compress')                # (before any table is evaluated or byte written)
         table_h, crc = self.host_table(min_v, max_v, device, want_crc=True)
         if info is not None:
             info['table_crc'] = crc

@@ -1413,15 +1413,28 @@ def desymbolize(sym, min_v):
     return out
 
 
+def check_symbol_range(min_v, max_v, what='latent'):
+    """Raise PcgcError unless [min_v, max_v] is a range int16 symbols can code: both finite and fewer than 32768 values (the reference has the
+    same limit, entropy_model.py:151-176, and wraps silently beyond it).  A NaN or infinite latent shows here: the device's min / max order
+    NaN beyond the infinity of its sign.  Called with the range that comes back with the symbols anyway: no launch, no copy."""
+    lo, hi = float(min_v), float(max_v)
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise PcgcError(f'{what}: the rounded values range from {lo} to {hi}: a latent that is not finite cannot be coded')
+    if hi - lo + 1 >= 32768:
+        raise PcgcError(f'{what}: the rounded values range from {lo:.0f} to {hi:.0f}, an alphabet of {hi - lo + 1:.0f} symbols; '
+                        'int16 symbols code at most 32767')
+
+
 def quantize_symbols(feats):
     """-> (min_v, max_v as np.float32, sym int16 ndarray of feats.shape): round + symbol range + symbolise on the device,
-    ONE synchronising device->host copy of [min | max | symbols]."""
+    ONE synchronising device->host copy of [min | max | symbols].  Raises PcgcError for a range int16 symbols cannot code."""
     feats = _f32(feats).contiguous()
     n = feats.numel()
     buf = torch.empty(4 + n, dtype=torch.int16, device=feats.device)          # [minmax as 2 fp32 = 4 int16 | sym]
     check(lib().pcgc_quantize_symbols(_p(feats), n, _p(buf), buf.data_ptr() + 8, _stream(feats)), 'quantize_symbols')
     host = buf.cpu().numpy()
     mm = host[:4].view(np.float32)
+    check_symbol_range(mm[0], mm[1], 'quantize_symbols')
     return np.float32(mm[0]), np.float32(mm[1]), host[4:].reshape(feats.shape)
 
 
@@ -1438,6 +1451,8 @@ def quantize_symbols_segments(feats, seg_rows):
           'quantize_symbols_segments')
     host = buf.cpu().numpy()
     mm = host[:4 * B].view(np.float32).reshape(B, 2)
+    for b, (lo, hi) in enumerate(mm):
+        check_symbol_range(lo, hi, f'quantize_symbols_segments: item {b}')
     return [(np.float32(a), np.float32(b)) for a, b in mm], host[4 * B:].reshape(n, C)
 
 
