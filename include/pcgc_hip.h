@@ -347,6 +347,44 @@ int pcgc_neg_log2_sum(const float* x, int ld, int64_t n, int C, double* bits /*[
 int pcgc_bce_logits(const float* logits, int64_t ld, int64_t n, const uint8_t* truth /*[dev n]*/, const uint8_t* pred /*[dev n] or NULL*/,
                     double* bce, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- backward pass of the training graph (trainer.py:127-134 `sum_loss.backward()`; csrc/grad.hip).  None of this is on the encode/decode
+ *      path.  No floating-point atomics: every reduction has a fixed order (per-workgroup partials in `workspace`, added in ascending
+ *      workgroup order by a second stage) and every grid is a function of the shapes alone, so gradients are bitwise reproducible.
+ *      The INPUT gradient of a convolution is a forward gather convolution (pcgc_conv_gather, Cout -> Cin) through a transposed map:
+ *      k3 on one level: the same map with W'[k] = W[26 - k]^T (the map is its own transpose under k <-> 26 - k, in both offset orders);
+ *      k2 s2 down / generative up: pcgc_kmap_invert of the forward map (up on an unpruned level: inv[j][p] = 8 p + j) with W[k]^T. ---- */
+/* Weight gradient of MinkowskiConvolution (k3 / k1 / k2 s2) through its forward map nbr [K, n_out] (NULL: identity, K = 1):
+ *   gW[k][a][b] = sum over present pairs o of x[nbr[k][o]][a] * gy[o][b]   [K, Cin, Cout];   gb[b] = sum_o gy[o][b] (NULL: not wanted).
+ * x [n_in rows, ld x_ld], gy [n_out rows, ld gy_ld] (column slices allowed), 1 <= Cin, Cout <= 64.  fp32 MFMA (v_mfma_f32_16x16x4_f32) with
+ * the gathered, transposed x rows as the A operand; channel counts below 16 run in a zero-padded tile.  workspace: 4-byte aligned,
+ * pcgc_conv_wgrad_workspace_bytes(K, n_out, Cin, Cout) bytes; a workgroup covers pcgc_conv_wgrad_rows_per_group(..) consecutive rows. */
+size_t pcgc_conv_wgrad_workspace_bytes(int K, int64_t n_rows, int Cin, int Cout);
+int64_t pcgc_conv_wgrad_rows_per_group(int K, int64_t n_rows, int Cin, int Cout);
+int pcgc_conv_wgrad(const int32_t* nbr, int K, int64_t n_out, const float* x, int64_t n_in, int Cin, int x_ld, const float* gy, int Cout,
+                    int gy_ld, float* gW, float* gb, void* workspace, size_t workspace_bytes, void* stream);
+/* The same for MinkowskiGenerativeConvolutionTranspose(k=2,s=2): gW[j][a][b] = sum_p x[p][a] * gy[8 p + j][b], gb[b] = sum over all 8 n_in rows
+ * of gy.  rows (or NULL): input row p is row rows[p] of x (a pruned level read in place, as pcgc_conv_up2_gather reads it); x has x_rows rows.
+ * workspace: pcgc_conv_wgrad_workspace_bytes(8, n_in, Cin, Cout). */
+int pcgc_conv_up2_wgrad(int64_t n_in, const float* x, int64_t x_rows, int Cin, int x_ld, const int32_t* rows, const float* gy, int Cout,
+                        int gy_ld, float* gW, float* gb, void* workspace, size_t workspace_bytes, void* stream);
+/* inv [K, n_in]: inv[k][nbr[k][o]] = o for every present pair of nbr [K, n_out], -1 elsewhere.  For a fixed k the map o -> nbr[k][o] must be
+ * injective (true for k3, k2 s2 down and generative-up maps). */
+int pcgc_kmap_invert(const int32_t* nbr, int K, int64_t n_out, int64_t n_in, int32_t* inv /*[dev K,n_in]*/, void* stream);
+/* adjoint of MinkowskiReLU: out = g where y > 0 (y = the ReLU's output or input), else 0; [n, C] views with leading dimensions */
+int pcgc_relu_bwd(const float* g, int g_ld, const float* y, int y_ld, int64_t n, int C, float* out, int out_ld, void* stream);
+/* adjoint of a row gather (pcgc_gather_rows_f32_ld / pcgc_compact_feats): gx [n_out, C] (ld gx_ld) = 0, then gx[orig[r]] = gy[r], r < n_rows;
+ * orig holds distinct rows */
+int pcgc_scatter_rows(const float* gy, int C, int gy_ld, const int32_t* orig, int64_t n_rows, float* gx, int64_t n_out, int gx_ld, void* stream);
+/* gradient of pcgc_bce_logits' bce with respect to the logits: g[i] = scale * (sigmoid(z_i) - t_i) / ln 2 (fp64, rounded once); g [n] dense */
+int pcgc_bce_logits_bwd(const float* logits, int64_t ld, int64_t n, const uint8_t* truth, double scale, float* g /*[dev n]*/, void* stream);
+/* gradient of pcgc_eb_likelihood's bits (= -sum log2 max(likelihood, bound)), times `scale`: gy [n, C] dense = d bits / d feats and gparams
+ * [44 C] in the packing of `params` (through softplus of the matrices and tanh of the factors; the sign of entropy_model.py:124 is a
+ * constant; an element whose likelihood is below the bound contributes zero: Low_bound.backward, entropy_model.py:27-39).  fp64 throughout,
+ * parameter sums reduced in fp64 in a fixed order, one rounding.  workspace: 8-byte aligned, pcgc_eb_bwd_workspace_bytes(n, C). */
+size_t pcgc_eb_bwd_workspace_bytes(int64_t n, int C);
+int pcgc_eb_likelihood_bwd(const float* feats, int ld, int64_t n, int C, const float* params /*[dev 44 C]*/, float bound, double scale,
+                           float* gy, float* gparams, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- range coder, bit-compatible with torchac 0.9.3 ‡ encode_float_cdf / decode_float_cdf
  *      (entropy_model.py:174,192).  HOST functions; symbols row-major [point, channel], one CDF row per channel. ---- */
 int64_t pcgc_rc_encode(const uint16_t* cdf /*[host C,Lp]*/, int C, int Lp, const int16_t* sym /*[host n]*/, int64_t n,

@@ -9,7 +9,8 @@ unmodified.  Same results as the fused graph, bit for bit (tests/test_gpu_parity
 `ME.SparseTensor(features=, coordinate_map_key=, coordinate_manager=)` (pcc_model.py:18-23: a tensor that shares another's coordinates)
 binds too: the key of a tensor is its coordinate level (sparse.CoordMap) and the manager a token that only has to be handed back.
 
-Not provided: MinkowskiEngine's other layers, and anything with a backward."""
+Not provided: MinkowskiEngine's other layers.  The layers of this module record no autograd graph; the backward pass of the same
+unfused operators lives in pcgcv2_amd/grad.py (`PCCModel.forward_train`), which pcgcv2_amd/trainer.py drives."""
 import torch
 
 from . import ops

@@ -88,6 +88,16 @@ SIGNATURES = {
     'pcgc_eb_likelihood': (ci, [vp, ci, i64, ci, vp, f32, vp, vp, vp, sz, vp]),
     'pcgc_neg_log2_sum': (ci, [vp, ci, i64, ci, vp, vp, sz, vp]),
     'pcgc_bce_logits': (ci, [vp, i64, i64, vp, vp, vp, vp, vp, sz, vp]),
+    'pcgc_conv_wgrad_workspace_bytes': (sz, [ci, i64, ci, ci]),
+    'pcgc_conv_wgrad_rows_per_group': (i64, [ci, i64, ci, ci]),
+    'pcgc_conv_wgrad': (ci, [vp, ci, i64, vp, i64, ci, ci, vp, ci, ci, vp, vp, vp, sz, vp]),
+    'pcgc_conv_up2_wgrad': (ci, [i64, vp, i64, ci, ci, vp, vp, ci, ci, vp, vp, vp, sz, vp]),
+    'pcgc_kmap_invert': (ci, [vp, ci, i64, i64, vp, vp]),
+    'pcgc_relu_bwd': (ci, [vp, ci, vp, ci, i64, ci, vp, ci, vp]),
+    'pcgc_scatter_rows': (ci, [vp, ci, ci, vp, i64, vp, i64, ci, vp]),
+    'pcgc_bce_logits_bwd': (ci, [vp, i64, i64, vp, C.c_double, vp, vp]),
+    'pcgc_eb_bwd_workspace_bytes': (sz, [i64, ci]),
+    'pcgc_eb_likelihood_bwd': (ci, [vp, ci, i64, ci, vp, f32, C.c_double, vp, vp, vp, sz, vp]),
     'pcgc_d1_cell_masks': (ci, [vp, i64, vp, vp, i64, vp, i64, vp]),
     'pcgc_d1_nn_cells': (ci, [vp, i64, vp, vp, i64, vp, vp, ci, i32, vp, vp, vp, vp]),
     'pcgc_d1_nn': (ci, [vp, i64, vp, vp, i64, vp, ci, vp, vp, vp, vp]),

@@ -1,7 +1,8 @@
 """Losses and classification metrics of the training graph (reference loss.py:1-41) and the record Trainer.test keeps per cloud
 (trainer.py:78-101), on the HIP operator set: same names and argument lists, so `from loss import get_bce, get_bits, get_metrics` binds.
 
-Forward values only.  Everything runs under torch.no_grad(): there are no backward kernels, so the results cannot be back-propagated.
+get_bce / get_bits / the metrics give forward values only and run under torch.no_grad(); `bce`, `bits` and `sum_loss` are their differentiable
+counterparts on the graph of PCCModel.forward_train (pcgcv2_amd/grad.py, csrc/grad.hip).
 Sums are accumulated in fp64 in a fixed order on the device (csrc/loss.hip) and rounded once to the fp32 scalar the reference returns;
 they are bitwise reproducible run to run.
 
@@ -33,6 +34,38 @@ def get_bits(likelihood):
     if lik.stride(-1) != 1:
         lik = lik.contiguous()
     return ops.neg_log2_sum(lik)[0].float()
+
+
+def bce(data, groud_truth, scale=1.0):
+    """Differentiable get_bce: scale * get_bce(data, groud_truth) as one autograd leaf over data.F (the logits of PCCModel.forward_train).
+    `scale` carries alpha / len(out_cls) of trainer.py:127-129 into the fp64 evaluation: value and gradient are each rounded once."""
+    from . import grad
+    return grad.BCE.apply(data.F, isin_mask(data.C, groud_truth), float(scale))
+
+
+def bits(likelihood, scale=1.0):
+    """Differentiable get_bits: scale * get_bits(likelihood) for the likelihood PCCModel.forward_train returned, differentiated with
+    respect to the latent and the bottleneck's 12 parameter tensors as one leaf (fp64 chain, one rounding; elements below the likelihood
+    bound contribute no gradient, as Low_bound.backward yields for this loss).  `scale` carries beta / len(x) of trainer.py:132-133."""
+    from . import grad
+    src = getattr(likelihood, '_rate_of', None)
+    if src is None:
+        raise ValueError('loss.bits: not the likelihood of PCCModel.forward_train (use get_bits for forward values)')
+    y_q, eb = src
+    params = [p for lst in (eb._matrices, eb._biases, eb._factors) for p in lst]
+    return grad.Bits.apply(y_q, float(scale), eb._likelihood_bound, *params)
+
+
+def sum_loss(out_set, n_points, alpha=1., beta=1.):
+    """trainer.py:127-134: alpha * sum_l get_bce(out_cls_l, truth_l) / len(out_cls_l) + beta * get_bits(likelihood) / len(x)
+    -> (sum_loss with a grad_fn, per-scale bce values, bpp)"""
+    total, bces = 0, []
+    for out_cls, ground_truth in zip(out_set['out_cls_list'], out_set['ground_truth_list']):
+        curr = bce(out_cls, ground_truth, scale=1.0 / float(len(out_cls)))
+        total = total + alpha * curr
+        bces.append(curr)
+    bpp = bits(out_set['likelihood'], scale=1.0 / float(n_points))
+    return total + beta * bpp, bces, bpp
 
 
 def _triple(TP, FN, FP):

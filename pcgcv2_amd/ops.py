@@ -1527,6 +1527,113 @@ def bce_logits(logits, truth, pred=None):
     return bce, counts
 
 
+# ------------------------------------------------------------------------------------------------ backward pass (csrc/grad.hip)
+def conv_wgrad_rows_per_group(K, n_rows, Cin, Cout):
+    """consecutive rows one workgroup of conv_wgrad reduces (a function of the shapes alone)"""
+    return int(lib().pcgc_conv_wgrad_rows_per_group(int(K), int(n_rows), int(Cin), int(Cout)))
+
+
+def _wgrad_ws(K, n_rows, Cin, Cout, device):
+    nbytes = int(lib().pcgc_conv_wgrad_workspace_bytes(K, n_rows, Cin, Cout))
+    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device), nbytes
+
+
+def conv_wgrad(nbr, x, gy, want_bias=True):
+    """Weight (and bias) gradient of a gather convolution through its forward map nbr [K, n_out] (None: identity, k1):
+    gW [K, Cin, Cout] = sum over present pairs of x[nbr[k][o]]^T gy[o]; gb [1, Cout] = column sums of gy (None unless want_bias).
+    x / gy: fp32 2-D views (column slices allowed)."""
+    _f32(x, 'x'); _f32(gy, 'gy')
+    Cin, Cout = x.shape[1], gy.shape[1]
+    if nbr is None:
+        K, n_out = 1, gy.shape[0]
+        if x.shape[0] != n_out:
+            raise PcgcError('conv_wgrad: identity map with different row counts')
+    else:
+        K, n_out = nbr.shape
+        _i32(nbr, 'nbr')
+        if gy.shape[0] != n_out:
+            raise PcgcError(f'conv_wgrad: gy has {gy.shape[0]} rows, the map {n_out}')
+    gW = torch.empty((K, Cin, Cout), dtype=torch.float32, device=x.device)
+    gb = torch.empty((1, Cout), dtype=torch.float32, device=x.device) if want_bias else None
+    ws, ws_bytes = _wgrad_ws(K, n_out, Cin, Cout, x.device)
+    check(lib().pcgc_conv_wgrad(_p(nbr), K, n_out, _p(x), x.shape[0], Cin, _ld(x), _p(gy), Cout, _ld(gy), _p(gW), _p(gb), _p(ws), ws_bytes,
+                                _stream(x)), 'conv_wgrad')
+    return gW, gb
+
+
+def conv_up2_wgrad(x, gy, rows=None, want_bias=True):
+    """Weight (and bias) gradient of the generative transpose k2 s2: gW [8, Cin, Cout] = sum_p x[p]^T gy[8 p + j]; rows: as in conv_up2."""
+    _f32(x, 'x'); _f32(gy, 'gy')
+    Cin, Cout = x.shape[1], gy.shape[1]
+    n_in = x.shape[0] if rows is None else rows.shape[0]
+    if gy.shape[0] != 8 * n_in:
+        raise PcgcError(f'conv_up2_wgrad: gy has {gy.shape[0]} rows for {n_in} input rows')
+    gW = torch.empty((8, Cin, Cout), dtype=torch.float32, device=x.device)
+    gb = torch.empty((1, Cout), dtype=torch.float32, device=x.device) if want_bias else None
+    ws, ws_bytes = _wgrad_ws(8, n_in, Cin, Cout, x.device)
+    check(lib().pcgc_conv_up2_wgrad(n_in, _p(x), x.shape[0], Cin, _ld(x), _p(None if rows is None else _i32(rows, 'rows')), _p(gy), Cout,
+                                    _ld(gy), _p(gW), _p(gb), _p(ws), ws_bytes, _stream(x)), 'conv_up2_wgrad')
+    return gW, gb
+
+
+def kmap_invert(nbr, n_in):
+    """inv [K, n_in] with inv[k][nbr[k][o]] = o for the present pairs of nbr [K, n_out], -1 elsewhere"""
+    K, n_out = nbr.shape
+    inv = torch.empty((K, int(n_in)), dtype=torch.int32, device=nbr.device)
+    check(lib().pcgc_kmap_invert(_p(_i32(nbr, 'nbr')), K, n_out, int(n_in), _p(inv), _stream(nbr)), 'kmap_invert')
+    return inv
+
+
+def kmap_up_inverse(n_in, device):
+    """the transposed map of a generative transpose on an unpruned children level: inv[j][p] = 8 p + j (no lookup)"""
+    return (8 * torch.arange(n_in, dtype=torch.int32, device=device)[None] + torch.arange(8, dtype=torch.int32, device=device)[:, None]).contiguous()
+
+
+def relu_bwd(g, y, out=None):
+    """g where y > 0, else 0 (2-D fp32 views; out may be a column slice)"""
+    _f32(g, 'g'); _f32(y, 'y')
+    if g.shape != y.shape:
+        raise PcgcError(f'relu_bwd: shapes {tuple(g.shape)} and {tuple(y.shape)} differ')
+    n, C = g.shape
+    if out is None:
+        out = torch.empty((n, C), dtype=torch.float32, device=g.device)
+    check(lib().pcgc_relu_bwd(_p(g), _ld(g), _p(y), _ld(y), n, C, _p(out), _ld(out), _stream(g)), 'relu_bwd')
+    return out
+
+
+def scatter_rows(gy, orig, n_out):
+    """adjoint of gather_rows / compact_feats: zeros [n_out, C] with row orig[r] = gy[r]"""
+    _f32(gy, 'gy')
+    C = gy.shape[1]
+    gx = torch.empty((int(n_out), C), dtype=torch.float32, device=gy.device)
+    check(lib().pcgc_scatter_rows(_p(gy), C, _ld(gy), _p(_i32(orig, 'orig')), orig.shape[0], _p(gx), int(n_out), C, _stream(gy)), 'scatter_rows')
+    return gx
+
+
+def bce_logits_bwd(logits, truth, scale=1.0):
+    """d(bce_logits' bce) / d logits times scale -> fp32 [n, 1]"""
+    _f32(logits, 'logits'); _dev(truth, torch.uint8, 'truth')
+    n = truth.shape[0]
+    if logits.shape[0] != n or logits.dim() > 2 or (logits.dim() == 2 and logits.shape[1] != 1):
+        raise PcgcError(f'bce_logits_bwd: logits {tuple(logits.shape)} against a mask of {n} rows')
+    g = torch.empty((n, 1), dtype=torch.float32, device=logits.device)
+    check(lib().pcgc_bce_logits_bwd(_p(logits), max(int(logits.stride(0)), 1), n, _p(truth), float(scale), _p(g), _stream(logits)), 'bce_logits_bwd')
+    return g
+
+
+def eb_likelihood_bwd(feats, params, bound=1e-9, scale=1.0):
+    """gradient of eb_likelihood's bits times scale -> (d / d feats fp32 [n, C], d / d params fp32 [44 C], the packing of `params`)"""
+    _f32(feats, 'feats')
+    n, C, ld = feats.shape[0], feats.shape[1], _ld(feats)
+    gy = torch.empty((n, C), dtype=torch.float32, device=feats.device)
+    gp = torch.empty(44 * C, dtype=torch.float32, device=feats.device)
+    nbytes = int(lib().pcgc_eb_bwd_workspace_bytes(n, C))
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=feats.device)
+    check(lib().pcgc_eb_likelihood_bwd(_p(feats), ld, n, C, _p(_f32(params, 'params')), float(bound), float(scale), _p(gy), _p(gp), _p(ws), nbytes,
+                                       _stream(feats)), 'eb_likelihood_bwd')
+    return gy, gp
+
+
 # ------------------------------------------------------------------------------------------------ D1 metric
 _D1_OFFSETS = {}
 

@@ -1,7 +1,7 @@
 """PCCModel (reference pcc_model.py:8-45): container wiring Encoder [1,16,32,64,32,8], Decoder [8,64,32,16] and
 EntropyBottleneck(8).  coder.Coder drives the encode/decode path; `forward` / `get_likelihood` are the forward half of the
-reference's training graph (rate estimate, per-scale logits, teacher-forced pruning).  They run under torch.no_grad(): no backward
-kernels exist."""
+reference's training graph (rate estimate, per-scale logits, teacher-forced pruning).  They run under torch.no_grad(); `forward_train` is the
+same graph with a backward pass (pcgcv2_amd/grad.py), which pcgcv2_amd/trainer.py drives."""
 import torch
 
 from .autoencoder import Encoder, Decoder
@@ -43,6 +43,19 @@ class PCCModel(torch.nn.Module):
                 'prior': y_q,
                 'likelihood': likelihood,
                 'ground_truth_list': ground_truth_list}
+
+    def forward_train(self, x, generator=None, record=None):
+        """forward(x, training=True) with an autograd graph (pcgcv2_amd/grad.py): the same dict with bit-equal values given the same
+        generator state; the feature tensors carry a grad_fn, and loss.bce / loss.bits of the result can be back-propagated to all 224
+        parameters.  record: optional dict that receives, per state-dict module name, what that layer's backward reads plus the level
+        coordinates and kept masks (tests)."""
+        from . import grad
+        return grad.forward_train(self, x, generator=generator, record=record)
+
+    def state_dict_reference(self):
+        """state_dict() in the reference's layout: whatever load_state_dict permutes on the way in (the kernel-offset convention), undone"""
+        from . import conventions
+        return conventions.permute_state_dict({k: v.detach().clone() for k, v in self.state_dict().items()})
 
 
 if __name__ == '__main__':
