@@ -547,6 +547,31 @@ int pcgc_table_cache(int mode);
  * zlib.crc32 for the same fields), folded with carry-less multiplies on long buffers.  HOST. */
 uint32_t pcgc_crc32(uint32_t crc, const uint8_t* buf, int64_t len);
 
+/* ---- training clouds from triangle meshes (the reference's generate_dataset.py:7-36, open3d on the CPU there).  The sampling
+ *      arithmetic is this project's own, exact in fp64 and counter-based (Philox4x32-10): sample i is a pure function of (seed, i).
+ *      csrc/mesh.hip states it; tests/mesh_reference.py restates it in numpy; DESIGN.md 8c explains it. ---- */
+/* ASCII OFF (header on one line, on two, or glued "OFF8 6 0") and OBJ (v; f with a, a/b, a/b/c, a//c tokens, 1-based or negative
+ * indices; other records skipped); polygons are fanned (v0, vi, vi+1).  counts[0] = vertices, counts[1] = triangles; verts = faces =
+ * NULL: sizes only.  0 ok; -1 the file cannot be read; -3 malformed or truncated; -4 a face names a missing vertex; -5 buffers too
+ * small.  HOST. */
+int pcgc_mesh_read(const char* path, double* verts /*[host vcap,3]*/, int64_t vcap, int32_t* faces /*[host fcap,3]*/, int64_t fcap,
+                   int64_t* counts /*[host 2]*/);
+/* cdf[t] = sum of the areas 0.5 |(B-A) x (C-A)| of triangles 0..t, in an order that depends on T alone (bitwise reproducible, no
+ * floating-point atomics) and never decreasing.  A face with an index outside [0, V) has area 0 and is counted in *bad_faces. */
+size_t pcgc_mesh_cdf_workspace_bytes(int64_t T);
+int pcgc_mesh_area_cdf(const double* verts /*[dev V,3]*/, int64_t V, const int32_t* faces /*[dev T,3]*/, int64_t T,
+                       double* cdf /*[dev T]*/, int32_t* bad_faces /*[dev 1]*/, void* workspace, size_t workspace_bytes, void* stream);
+/* samples first .. first+n-1: the triangle each falls on and / or its point */
+int pcgc_mesh_sample(const double* verts, int64_t V, const int32_t* faces, const double* cdf, int64_t T, uint64_t seed, uint64_t first,
+                     int64_t n, int32_t* tri /*[dev n] or NULL*/, double* points /*[dev n,3] or NULL*/, void* stream);
+/* mesh2pc after the file read: samples 0..n-1, q = p . R, d = q - min q, rint((d / max d) * resolution), distinct rows (0, x, y, z) in
+ * (z, y, x) order.  1 <= resolution <= 1023.  *count = rows found (the first `cap` of them are written; min(n, (resolution+1)^3)
+ * always suffices); -1: the total area is not positive and finite; -2: max d is not (every sample fell on one value). */
+size_t pcgc_mesh_voxelize_workspace_bytes(int32_t resolution);
+int pcgc_mesh_voxelize(const double* verts, int64_t V, const int32_t* faces, const double* cdf, int64_t T, uint64_t seed, int64_t n,
+                       const double* R /*[host 9] row-major*/, int32_t resolution, int32_t* out /*[dev cap,4]*/, int64_t cap,
+                       int32_t* count /*[dev 1]*/, void* workspace /*[dev] 64-byte aligned*/, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -139,6 +139,12 @@ SIGNATURES = {
     'pcgc_crc32': (C.c_uint32, [C.c_uint32, vp, i64]),
     'pcgc_ply_read_ascii_geo': (i64, [C.c_char_p, vp, i64]),
     'pcgc_ply_write_ascii_geo': (ci, [C.c_char_p, vp, i64]),
+    'pcgc_mesh_read': (ci, [C.c_char_p, vp, i64, vp, i64, vp]),
+    'pcgc_mesh_cdf_workspace_bytes': (sz, [i64]),
+    'pcgc_mesh_area_cdf': (ci, [vp, i64, vp, i64, vp, vp, vp, sz, vp]),
+    'pcgc_mesh_sample': (ci, [vp, i64, vp, vp, i64, C.c_uint64, C.c_uint64, i64, vp, vp, vp]),
+    'pcgc_mesh_voxelize_workspace_bytes': (sz, [i32]),
+    'pcgc_mesh_voxelize': (ci, [vp, i64, vp, vp, i64, C.c_uint64, i64, vp, i32, vp, i64, vp, vp, sz, vp]),
 }
 
 

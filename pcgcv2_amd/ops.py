@@ -1813,6 +1813,81 @@ def d2_reduce(c2c, c2p):
     return sm, s
 
 
+# ------------------------------------------------------------------------------------------------ meshes -> training clouds
+def _mesh(verts, faces):
+    _dev(verts, torch.float64, 'verts')
+    _dev(faces, torch.int32, 'faces')
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise PcgcError('a mesh is verts [V,3] float64 and faces [T,3] int32')
+    return verts.shape[0], faces.shape[0]
+
+
+def _u64(v, what):
+    v = int(v)
+    if not 0 <= v < 1 << 64:
+        raise ValueError(f'{what} must be an unsigned 64-bit integer, got {v}')
+    return v
+
+
+def mesh_area_cdf(verts, faces):
+    """-> float64 [T]: inclusive sums of the triangle areas, never decreasing and bitwise reproducible (fixed summation order).
+    Raises PcgcError if a face names a vertex outside [0, V) (reads one int32 back)."""
+    V, T = _mesh(verts, faces)
+    cdf = torch.empty(T, dtype=torch.float64, device=verts.device)
+    bad = torch.empty(1, dtype=torch.int32, device=verts.device)
+    ws_bytes = int(lib().pcgc_mesh_cdf_workspace_bytes(T))
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=verts.device)
+    check(lib().pcgc_mesh_area_cdf(_p(verts), V, _p(faces), T, _p(cdf), _p(bad), _p(ws), ws_bytes, _stream(verts)), 'mesh_area_cdf')
+    n_bad = int(bad.item())
+    if n_bad:
+        raise PcgcError(f'mesh_area_cdf: {n_bad} of {T} faces name a vertex outside [0, {V})')
+    return cdf
+
+
+def mesh_sample(verts, faces, cdf, seed, first, n, want_tri=True, want_points=True):
+    """Samples first .. first+n-1 of `seed` -> (tri int32 [n] or None, points float64 [n,3] or None).  Sample i depends on (seed, i) only."""
+    V, T = _mesh(verts, faces)
+    _dev(cdf, torch.float64, 'cdf')
+    if cdf.shape != (T,):
+        raise PcgcError(f'cdf: expected shape ({T},), got {tuple(cdf.shape)}')
+    n = int(n)
+    tri = torch.empty(max(n, 0), dtype=torch.int32, device=verts.device) if want_tri else None
+    pts = torch.empty((max(n, 0), 3), dtype=torch.float64, device=verts.device) if want_points else None
+    check(lib().pcgc_mesh_sample(_p(verts), V, _p(faces), _p(cdf), T, _u64(seed, 'seed'), _u64(first, 'first'), n, _p(tri), _p(pts),
+                                 _stream(verts)), 'mesh_sample')
+    return tri, pts
+
+
+def mesh_voxelize(verts, faces, cdf, seed, n, R, resolution):
+    """mesh2pc after the file read: n samples, rotated by R (3x3, points . R), normalised by the scalar min and max of all coordinates,
+    rounded half-even onto 0..resolution -> the distinct voxels as int32 [M,4] rows (0, x, y, z) in (z, y, x) order.  Raises PcgcError
+    for n < 1, a resolution outside 1..1023, a total area that is not positive, or samples that all fall on one value."""
+    V, T = _mesh(verts, faces)
+    _dev(cdf, torch.float64, 'cdf')
+    if cdf.shape != (T,):
+        raise PcgcError(f'cdf: expected shape ({T},), got {tuple(cdf.shape)}')
+    R = np.ascontiguousarray(R, dtype=np.float64)
+    if R.shape != (3, 3):
+        raise PcgcError(f'rotation: expected a 3x3 matrix, got shape {R.shape}')
+    n, resolution = int(n), int(resolution)
+    dev = verts.device
+    ws_bytes = int(lib().pcgc_mesh_voxelize_workspace_bytes(max(min(resolution, 1 << 20), 0)))     # (0 for an unsupported resolution)
+    ws = torch.empty(max(ws_bytes, 64), dtype=torch.uint8, device=dev)
+    cap = max(min(n, (resolution + 1) ** 3), 0) if ws_bytes else 0
+    out = torch.empty((max(cap, 1), 4), dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    check(lib().pcgc_mesh_voxelize(_p(verts), V, _p(faces), _p(cdf), T, _u64(seed, 'seed'), n, R.ctypes.data, resolution, _p(out), cap,
+                                   _p(count), _p(ws), ws_bytes, _stream(verts)), 'mesh_voxelize')
+    m = int(count.item())
+    if m == -1:
+        raise PcgcError('mesh_voxelize: the total area of the mesh is not a positive finite number')
+    if m < 0:
+        raise PcgcError('mesh_voxelize: every sample has the same coordinate value (max - min is not a positive finite number)')
+    if m > cap:
+        raise PcgcError(f'mesh_voxelize: {m} voxels from {n} samples')           # (cannot happen: one bit per sample at most)
+    return out[:m]
+
+
 # ------------------------------------------------------------------------------------------------ host codecs (numpy)
 def _np(a, dt):
     return np.ascontiguousarray(a, dtype=dt)
