@@ -572,6 +572,22 @@ int pcgc_mesh_voxelize(const double* verts, int64_t V, const int32_t* faces, con
                        const double* R /*[host 9] row-major*/, int32_t resolution, int32_t* out /*[dev cap,4]*/, int64_t cap,
                        int32_t* count /*[dev 1]*/, void* workspace /*[dev] 64-byte aligned*/, size_t workspace_bytes, void* stream);
 
+/* ---- batches out of the data loader's device-resident arena (pcgcv2_amd/data_loader.py, csrc/collate.hip) ---- */
+#define PCGC_COLLATE_MAX_ITEMS 16
+/* One cloud of a batch: `rows` rows of three values, `width` bytes each (1: uint8, 2: uint16, 4: int32), packed from byte `offset` of
+ * the arena (a multiple of 16) in file order.  symmetry = perm + 6 * flips, one of the 48 symmetries of the cube: a row v becomes w with
+ * w[a] = (flips >> a & 1) ? extent - v[a] : v[a], then out = w[perm], perm counted through (0,1,2) (0,2,1) (1,0,2) (1,2,0) (2,0,1)
+ * (2,1,0); 0 leaves the row as it is.  first_row = the sum of the rows of the items before it. */
+typedef struct pcgc_collate_item {
+    int64_t offset;
+    int32_t first_row, rows, width, symmetry, extent, reserved;
+} pcgc_collate_item;
+/* coords_out[first_row + r] = (item, x, y, z), feats_out[first_row + r] = 1.0f for every row of every item, N = the sum of the rows; one
+ * launch, the items by value in the kernel arguments.  n_items == 0 and N == 0 launch nothing.  The caller vouches that every item lies
+ * inside the arena (ops.collate_rows checks it). */
+int pcgc_collate_rows(const uint8_t* arena /*[dev] 16-byte aligned*/, const pcgc_collate_item* items /*[host n_items]*/, int n_items,
+                      int32_t* coords_out /*[dev N,4] 16-byte aligned*/, float* feats_out /*[dev N,1]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

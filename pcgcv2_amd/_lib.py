@@ -145,7 +145,13 @@ SIGNATURES = {
     'pcgc_mesh_sample': (ci, [vp, i64, vp, vp, i64, C.c_uint64, C.c_uint64, i64, vp, vp, vp]),
     'pcgc_mesh_voxelize_workspace_bytes': (sz, [i32]),
     'pcgc_mesh_voxelize': (ci, [vp, i64, vp, vp, i64, C.c_uint64, i64, vp, i32, vp, i64, vp, vp, sz, vp]),
+    'pcgc_collate_rows': (ci, [vp, vp, ci, vp, vp, vp]),
 }
+
+
+class CollateItem(C.Structure):
+    """pcgc_collate_item of include/pcgc_hip.h"""
+    _fields_ = [('offset', i64), ('first_row', i32), ('rows', i32), ('width', i32), ('symmetry', i32), ('extent', i32), ('reserved', i32)]
 
 
 class PcgcError(RuntimeError):

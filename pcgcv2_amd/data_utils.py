@@ -31,6 +31,28 @@ def write_ply_ascii_geo(filedir, coords):
         raise PcgcError(f'cannot write {filedir}')
 
 
+def _h5py():
+    try:
+        import h5py
+    except ImportError as e:
+        raise ImportError('h5py is not installed: the .h5 patch files of the reference need it (PLY files do not)') from e
+    return h5py
+
+
+def read_h5_geo(filedir):
+    """data_utils.py:6-10: dataset 'data', columns 0:3 as int."""
+    with _h5py().File(filedir, 'r') as h:
+        pc = h['data'][:]
+    return pc[:, 0:3].astype('int')
+
+
+def write_h5_geo(filedir, coords):
+    """data_utils.py:12-17: dataset 'data' as uint8 (coordinates past 255 wrap, as in the reference)."""
+    data = np.asarray(coords).astype('uint8')
+    with _h5py().File(filedir, 'w') as h:
+        h.create_dataset('data', data=data, shape=data.shape)
+
+
 def array2vector(array, step):
     """data_utils.py:55-61 (host-side; the device path is ops.sort_zyx)."""
     array = torch.as_tensor(array).long().cpu()

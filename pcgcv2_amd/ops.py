@@ -1888,6 +1888,43 @@ def mesh_voxelize(verts, faces, cdf, seed, n, R, resolution):
     return out[:m]
 
 
+# ------------------------------------------------------------------------------------------------ data loader: batches out of the arena
+COLLATE_MAX_ITEMS = 16
+
+
+def collate_rows(arena, items, out=None):
+    """One batch out of the data loader's arena in one launch -> (coords int32 [N, 4] rows (item, x, y, z), feats float32 [N, 1] of ones).
+    arena: uint8 device tensor; items: up to 16 of (byte offset, rows, width in bytes 1 / 2 / 4, symmetry code 0..47, extent), each cloud
+    three packed values per row from its offset (a multiple of 16) in file order.  out = (coords, feats) with at least N rows writes into
+    those and returns their first N rows; rows past N are not touched.  No items or no rows: nothing is launched."""
+    from ._lib import CollateItem
+    _dev(arena, torch.uint8, 'arena')
+    items = list(items)
+    if len(items) > COLLATE_MAX_ITEMS:
+        raise ValueError(f'a batch holds at most {COLLATE_MAX_ITEMS} items, got {len(items)}')
+    table = (CollateItem * max(len(items), 1))()
+    n = 0
+    for k, (offset, rows, width, symmetry, extent) in enumerate(items):
+        offset, rows, width = int(offset), int(rows), int(width)
+        if width not in (1, 2, 4) or rows < 0 or offset < 0 or offset % 16 or offset + 3 * width * rows > arena.numel():
+            raise PcgcError(f'collate_rows: item {k} (offset {offset}, {rows} rows of 3 x {width} bytes) does not lie in the arena of '
+                            f'{arena.numel()} bytes on a 16-byte boundary')
+        if not 0 <= int(symmetry) < 48:
+            raise ValueError(f'collate_rows: symmetry code must be 0..47, got {symmetry}')
+        table[k] = CollateItem(offset, n, rows, width, int(symmetry), int(extent), 0)
+        n += rows
+    if out is None:
+        coords = torch.empty((n, 4), dtype=torch.int32, device=arena.device)
+        feats = torch.empty((n, 1), dtype=torch.float32, device=arena.device)
+    else:
+        coords, feats = _i32(out[0], 'out coords'), _dev(out[1], torch.float32, 'out feats')
+        if coords.dim() != 2 or coords.shape[1] != 4 or coords.shape[0] < n or feats.numel() < n or feats.device != coords.device \
+                or coords.device != arena.device:
+            raise PcgcError(f'collate_rows: out must be int32 [>= {n}, 4] and float32 [>= {n}, 1] on the arena\'s device')
+    check(lib().pcgc_collate_rows(_p(arena), table, len(items), _p(coords), _p(feats), _stream(arena)), 'collate_rows')
+    return coords[:n], feats[:n]
+
+
 # ------------------------------------------------------------------------------------------------ host codecs (numpy)
 def _np(a, dt):
     return np.ascontiguousarray(a, dtype=dt)

@@ -1,7 +1,10 @@
-"""Training CLI (reference train.py) with the reference's flags and defaults.  The dataset is a glob of ASCII PLY files read by the
-package's reader (the reference's HDF5 patch files are not supported); batches are collated by sparse_collate.
+"""Training CLI (reference train.py) with the reference's flags and defaults.  The dataset is a glob of cloud files.  Without a loader
+flag the files are ASCII PLY, re-read for every batch by PlyLoader and collated by sparse_collate on the host.  With --num_workers,
+--device_cache or --augment the loaders come from data_loader.make_data_loader: clouds are cached after the first read,
+on the GPU under --device_cache, and the reference's HDF5 patch files (.h5) are read too where h5py is installed.
 
     python -m pcgcv2_amd.train --dataset 'clouds/*.ply' --batch_size 8 --epoch 50 --prefix tp
+    python -m pcgcv2_amd.train --dataset 'clouds/*.ply' --batch_size 8 --epoch 50 --prefix tp --device_cache --augment --num_workers 4
 """
 import argparse
 import glob
@@ -28,6 +31,9 @@ def parse_args(argv=None):
     parser.add_argument('--epoch', type=int, default=50)
     parser.add_argument('--check_time', type=float, default=10, help='frequency for recording state (min).')
     parser.add_argument('--prefix', type=str, default='tp', help='prefix of checkpoints/logger, etc.')
+    parser.add_argument('--num_workers', type=int, default=0, help='host threads parsing files ahead of the training loop (data_loader).')
+    parser.add_argument('--device_cache', action='store_true', help='keep every cloud read so far on the GPU and collate batches there.')
+    parser.add_argument('--augment', action='store_true', help='one of the 48 symmetries of the cube per training cloud and batch.')
     return parser.parse_args(argv)
 
 
@@ -58,8 +64,15 @@ def main(argv=None):
     if not filedirs:
         raise SystemExit(f'no file matches {args.dataset!r}')
     n_test = round(len(filedirs) / 10)
-    train_loader = PlyLoader(filedirs[n_test:], args.batch_size, shuffle=True)
-    test_loader = PlyLoader(filedirs[:n_test], args.batch_size, shuffle=False)
+    if args.num_workers or args.device_cache or args.augment:
+        from .data_loader import PCDataset, make_data_loader
+        train_loader = make_data_loader(PCDataset(filedirs[n_test:]), args.batch_size, shuffle=True, num_workers=args.num_workers,
+                                        device_cache=args.device_cache, augment=args.augment, device=trainer.device if args.device_cache else None)
+        test_loader = make_data_loader(PCDataset(filedirs[:n_test]), args.batch_size, shuffle=False, num_workers=args.num_workers,
+                                       device_cache=args.device_cache, augment=False, device=trainer.device if args.device_cache else None)
+    else:
+        train_loader = PlyLoader(filedirs[n_test:], args.batch_size, shuffle=True)
+        test_loader = PlyLoader(filedirs[:n_test], args.batch_size, shuffle=False)
     for epoch in range(0, args.epoch):
         if epoch > 0:
             trainer.config.lr = max(trainer.config.lr / 2, 1e-5)
