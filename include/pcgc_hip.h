@@ -487,6 +487,29 @@ size_t pcgc_d2_reduce_workspace_bytes(void);
 int pcgc_d2_reduce(const int64_t* c2c, const double* c2p, int64_t n, int64_t* c2c_sum_max, double* c2p_sum, void* workspace, size_t workspace_bytes,
                    void* stream);
 
+/* ---- Estimated surface normals of a voxelised cloud (csrc/normals.hip; nothing in the reference: its D2 figures assume clouds whose normals
+ *      another tool estimated).  Per row at voxel p: the neighbourhood is every DISTINCT voxel q of the row's batch with |q - p|^2 <= r2 (p
+ *      included); moments [n,10] = k, sum dx dy dz, sum dx^2 dy^2 dz^2 dxdy dxdz dydz over d = q - p (exact); S = k sum(d d^T) - (sum d)(sum d)^T;
+ *      lam [n,3] = eigenvalues of S ascending (fp64); valid = k >= 3 and rank S >= 2 (on the integers); normals [n,3] = unit eigenvector of
+ *      lam[0], (0, 0, 0) where not valid; count = k.  Every duplicate row receives its voxel's result.  orient 0: the component of largest
+ *      magnitude is positive; 1: away from the centroid of the batch's distinct voxels; 2: towards viewpoint [host 3]; an exactly zero dot
+ *      product falls back to rule 0.  The cloud is given by its original rows (coords) and by its D2 index exactly as for pcgc_d2_count
+ *      (qs, perm, cell hash, masks, voxel hash, runlen); ball = pcgc_normals_ball_masks(r2) uploaded by the caller.  r2 outside 1 .. 64 is an
+ *      error (-2), never clamped; coordinates must have passed pcgc_coords_check_order.  Bitwise reproducible, independent of the row order. */
+/* ball [(2 C + 1)^3][64], C = ceil(floor(sqrt r2) / 4): bit b of ball[t][l] = voxel b of the cell at offset t (x fastest, from -C) lies within
+ * r2 of voxel l of the centre cell.  HOST.  -> number of masks (table = NULL: only that), < 0: error */
+int64_t pcgc_normals_ball_masks(int32_t r2, uint64_t* table /*[host] or NULL*/);
+size_t pcgc_normals_workspace_bytes(int64_t n);
+int pcgc_normals_estimate(const int32_t* coords /*[dev n,4]*/, int64_t n, const int32_t* qs /*[dev n,4]*/, const int32_t* perm,
+                          const uint64_t* cell_keys, const int32_t* cell_vals, int64_t cell_cap, const uint64_t* masks, const uint64_t* keys,
+                          const int32_t* vals, int64_t cap, const int32_t* runlen, const uint64_t* ball /*[dev]*/, int32_t r2, int orient,
+                          const double* viewpoint /*[host 3] or NULL*/, int64_t* moments /*[dev n,10]*/, double* normals /*[dev n,3]*/,
+                          double* lam /*[dev n,3]*/, int32_t* count /*[dev n]*/, uint8_t* valid /*[dev n]*/, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* process-wide A/B knob of the moments pass: 0 = one wave per occupied 4 x 4 x 4 cell (default), 1 = one thread per voxel.  Same results.
+ * -> the previous mode */
+int pcgc_set_normals_mapping(int mode);
+
 /* ---- ASCII PLY geometry I/O (data_utils.py:19-48: read_ply_ascii_geo / write_ply_ascii_geo), HOST.
  *      read: returns the number of data rows (call with xyz = NULL to size the buffer); same acceptance rule as the
  *      reference (a line is data iff all its ' '-separated tokens parse as floats); columns 0:3 truncated to int. ---- */

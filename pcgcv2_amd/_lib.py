@@ -114,6 +114,10 @@ SIGNATURES = {
     'pcgc_d2_c2p': (ci, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
     'pcgc_d2_reduce_workspace_bytes': (sz, []),
     'pcgc_d2_reduce': (ci, [vp, vp, i64, vp, vp, vp, sz, vp]),
+    'pcgc_normals_ball_masks': (i64, [i32, vp]),
+    'pcgc_normals_workspace_bytes': (sz, [i64]),
+    'pcgc_normals_estimate': (ci, [vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, i32, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'pcgc_set_normals_mapping': (ci, [ci]),
     'pcgc_rc_encode': (i64, [vp, ci, ci, vp, i64, vp, i64]),
     'pcgc_rc_decode': (ci, [vp, ci, ci, vp, i64, vp, i64]),
     'pcgc_set_rc_impl': (ci, [ci]),

@@ -31,6 +31,26 @@ def write_ply_ascii_geo(filedir, coords):
         raise PcgcError(f'cannot write {filedir}')
 
 
+def write_ply_ascii_geo_normals(filedir, coords, normals):
+    """ASCII PLY with `property float x/y/z/nx/ny/nz` (what pc_error.read_ply_ascii_with_normals parses): integer coordinate text, the
+    normals as float32 with 9 significant digits (they read back to the same float32)."""
+    import pandas as pd
+    coords = np.asarray(coords).reshape(-1, 3)
+    normals = np.asarray(normals, dtype=np.float32).reshape(-1, 3)
+    if len(coords) != len(normals):
+        raise ValueError(f'{len(coords)} points but {len(normals)} normals')
+    if not np.array_equal(coords, np.rint(coords)):
+        raise ValueError('write_ply_ascii_geo_normals: coordinates must be integers (a voxelised cloud)')
+    frame = pd.DataFrame(coords.astype(np.int64))
+    for j in range(3):
+        frame[3 + j] = normals[:, j].astype(np.float64)
+    with open(filedir, 'w', newline='') as f:
+        f.write('ply\nformat ascii 1.0\nelement vertex %d\n' % len(coords))
+        f.write(''.join(f'property float {c}\n' for c in ('x', 'y', 'z', 'nx', 'ny', 'nz')))
+        f.write('end_header\n')
+        frame.to_csv(f, sep=' ', header=False, index=False, float_format='%.9g', lineterminator='\n')
+
+
 def _h5py():
     try:
         import h5py

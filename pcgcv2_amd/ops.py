@@ -1813,6 +1813,74 @@ def d2_reduce(c2c, c2p):
     return sm, s
 
 
+# ------------------------------------------------------------------------------------------------ estimated normals (csrc/normals.hip)
+NORMALS_MAX_R2 = 64
+_NORMALS_BALL = {}
+
+
+def _normals_ball(device, r2):
+    """the ball masks of pcgc_normals_ball_masks(r2) on `device`: built once per (device, r2)"""
+    key = (str(device), int(r2))
+    if key not in _NORMALS_BALL:
+        n = int(lib().pcgc_normals_ball_masks(int(r2), None))
+        if n < 0:
+            check(n, 'normals_ball_masks')
+        tab = np.empty(n, np.uint64)
+        if int(lib().pcgc_normals_ball_masks(int(r2), tab.ctypes.data)) != n:
+            raise PcgcError('normals_ball_masks: size changed')
+        _NORMALS_BALL[key] = torch.from_numpy(tab.view(np.int64)).to(device)
+    return _NORMALS_BALL[key]
+
+
+def estimate_normals(coords, r2=16, orient='centroid', index=None, want_moments=False):
+    """Surface normals of a voxelised cloud from fixed-radius neighbourhoods (include/pcgc_hip.h, pcgc_normals_estimate).
+    coords: int32 [N,4] (batch, x, y, z) device tensor or a sparse tensor; r2: integer squared radius, 1 .. 64; orient: 'centroid' (away from
+    the centroid of the row's batch), a viewpoint (x, y, z) (towards it) or None (largest component positive); index: a D2Index of `coords`
+    to reuse.  -> (normals float64 [N,3], lam float64 [N,3] ascending, count int32 [N], valid bool [N]) and, with want_moments, the exact
+    moments int64 [N,10].  Rows that are not valid (fewer than 3 neighbours, or all of them on one line) have normal (0, 0, 0)."""
+    coords = coords.C if hasattr(coords, 'C') else coords
+    coords = _i32(coords, 'coords')
+    if coords.dim() != 2 or coords.shape[1] != 4:
+        raise PcgcError(f'estimate_normals: coords must be [N,4], got {tuple(coords.shape)}')
+    if isinstance(r2, bool) or int(r2) != r2 or not 1 <= int(r2) <= NORMALS_MAX_R2:
+        raise ValueError(f'estimate_normals: r2 must be an integer in 1 .. {NORMALS_MAX_R2}, got {r2!r}')
+    r2 = int(r2)
+    view = None
+    if orient is None:
+        mode = 0
+    elif isinstance(orient, str):
+        if orient != 'centroid':
+            raise ValueError(f"estimate_normals: orient must be 'centroid', a viewpoint (x, y, z) or None, got {orient!r}")
+        mode = 1
+    else:
+        view = np.ascontiguousarray(np.asarray(orient, np.float64).reshape(-1))
+        if view.shape != (3,) or not np.isfinite(view).all():
+            raise ValueError(f'estimate_normals: a viewpoint is three finite numbers, got {orient!r}')
+        mode = 2
+    n, dev = coords.shape[0], coords.device
+    if n == 0:
+        out = (torch.empty((0, 3), dtype=torch.float64, device=dev), torch.empty((0, 3), dtype=torch.float64, device=dev),
+               torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.bool, device=dev))
+        return out + (torch.empty((0, 10), dtype=torch.int64, device=dev),) if want_moments else out
+    check_coords(coords, 'estimate_normals')
+    if index is None:
+        index = D2Index(coords)
+    elif index.n != n or index.coords.data_ptr() != coords.data_ptr():
+        raise PcgcError('estimate_normals: the index was built from another tensor')
+    ball = _normals_ball(dev, r2)
+    moments = torch.empty((n, 10), dtype=torch.int64, device=dev)
+    normals = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    lam = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    valid = torch.empty(n, dtype=torch.bool, device=dev)
+    ws_bytes = int(lib().pcgc_normals_workspace_bytes(n))
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    check(lib().pcgc_normals_estimate(_p(coords), n, _p(index.qs), _p(index.perm), *index.tables(), _p(ball), r2, mode,
+                                      None if view is None else view.ctypes.data, _p(moments), _p(normals), _p(lam), _p(count), _p(valid),
+                                      _p(ws), ws_bytes, _stream(coords)), 'normals_estimate')
+    return (normals, lam, count, valid, moments) if want_moments else (normals, lam, count, valid)
+
+
 # ------------------------------------------------------------------------------------------------ meshes -> training clouds
 def _mesh(verts, faces):
     _dev(verts, torch.float64, 'verts')

@@ -215,9 +215,20 @@ def lattice_coords(xyz, device, batch=0):
     return torch.from_numpy(out).to(device)
 
 
+def estimate_normals_device(coords, r2=16, orient='centroid'):
+    """Normals of a voxelised cloud estimated on the GPU: coords int32 [N,4] (batch, x, y, z) device tensor (or a sparse tensor), r2 the
+    integer squared radius of the neighbourhood (1 .. 64), orient 'centroid' | (x, y, z) viewpoint | None.
+    -> (normals float64 [N,3], lam float64 [N,3], count int32 [N], valid bool [N]), see ops.estimate_normals."""
+    from . import ops
+    return ops.estimate_normals(coords, r2=r2, orient=orient)
+
+
 def d2_psnr_device(a, na, b, res):
     """The columns of d2_psnr, computed on the GPU: a, b int32 [N,4] (batch, x, y, z) device tensors (or sparse tensors' .C), na the normals of
-    a ([Na,3], float32 or float64, used as fp64).  Neighbours are searched within the same batch index only.
+    a ([Na,3], float32 or float64, used as fp64) — or 'estimate' / a dict {'r2': .., 'orient': ..} of estimate_normals_device's options: the
+    normals are then estimated on a (ops.estimate_normals, through the index of a that the search builds anyway) and the result gains
+    `normals_r2` and `normals_invalid` (rows of a without a valid normal: they enter as (0, 0, 0)).  Such figures compare across our own
+    rates and runs, not with published D2 computed from a dataset's own normals.  Neighbours are searched within the same batch index only.
     Every row is a point of its own (duplicated rows are counted and appear in tie sets).  Tie sets: every point of the other cloud at the
     nearest squared distance, at most 30 — when more tie (e.g. 48 lattice points at d2 = 14) the 30 with the LOWEST row indices, as
     oracle/pcgc_oracle.py:d2_metrics keeps them (the host d2_psnr's k = 30 KD-tree query keeps an unspecified subset in that case).  Exact at
@@ -229,11 +240,22 @@ def d2_psnr_device(a, na, b, res):
     a, b = a.contiguous(), b.contiguous()
     if a.shape[0] == 0 or b.shape[0] == 0:
         raise ValueError('d2_psnr_device: empty point cloud')
-    if na.shape != (a.shape[0], 3):
+    estimate = None
+    if isinstance(na, (str, dict)):
+        if isinstance(na, str) and na != 'estimate':
+            raise ValueError(f"d2_psnr_device: normals are a tensor, 'estimate' or a dict of estimate_normals_device's options, got {na!r}")
+        estimate = {'r2': 16, 'orient': 'centroid', **(na if isinstance(na, dict) else {})}
+        if set(estimate) != {'r2', 'orient'}:
+            raise ValueError(f"d2_psnr_device: unknown normal-estimation options {sorted(set(estimate) - {'r2', 'orient'})}")
+    elif na.shape != (a.shape[0], 3):
         raise ValueError(f'd2_psnr_device: normals {tuple(na.shape)} do not match {a.shape[0]} points')
     ops.check_coords(a, 'd2_psnr_device: a'); ops.check_coords(b, 'd2_psnr_device: b')
-    na = torch.as_tensor(na).to(device=a.device, dtype=torch.float64).contiguous()
     ia, ib = ops.D2Index(a), ops.D2Index(b)
+    extra = {}
+    if estimate is not None:
+        na, _, _, ok = ops.estimate_normals(a, estimate['r2'], estimate['orient'], index=ia)
+        extra = {'normals_r2': int(estimate['r2']), 'normals_invalid': a.shape[0] - int(ok.sum().item())}
+    na = torch.as_tensor(na).to(device=a.device, dtype=torch.float64).contiguous()
     ab, ba = ops.d2_nn(a, ib), ops.d2_nn(b, ia)
     nb = ops.d2_normals(b.shape[0], ab, na, ba)
     sums = []
@@ -250,7 +272,7 @@ def d2_psnr_device(a, na, b, res):
             'mseF      (p2point)': max(mse1, mse2), 'mseF,PSNR (p2point)': psnr(max(mse1, mse2)),
             'h.        (p2point)': max(h1, h2), 'h.,PSNR   (p2point)': psnr(max(h1, h2)),
             'mse1      (p2plane)': pl1, 'mse1,PSNR (p2plane)': psnr(pl1), 'mse2      (p2plane)': pl2, 'mse2,PSNR (p2plane)': psnr(pl2),
-            'mseF      (p2plane)': max(pl1, pl2), 'mseF,PSNR (p2plane)': psnr(max(pl1, pl2))}
+            'mseF      (p2plane)': max(pl1, pl2), 'mseF,PSNR (p2plane)': psnr(max(pl1, pl2)), **extra}
 
 
 def pc_error(infile1, infile2, res, normal=False, show=False):

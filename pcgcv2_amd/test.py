@@ -9,7 +9,12 @@ input PLY (as the reference's `pc_error(..., normal=True)` does) and are compute
 
 metric='host' (the default) computes D1 / D2 like the reference: pc_error() on the input PLY and the decoded PLY.  metric='device' computes
 the same columns on the GPU (pc_error.d2_psnr_device, or d1_psnr_device for a cloud without normals): the input's raw rows and normals are
-read and uploaded once, the decoded cloud is taken from the decoder's tensor directly (its PLY is still written), no pc_error_d is run."""
+read and uploaded once, the decoded cloud is taken from the decoder's tensor directly (its PLY is still written), no pc_error_d is run.
+
+estimate_normals=R2 (`--estimate_normals [R2]`, off by default; metric='device' only): a cloud WITHOUT normals gets the D2 columns too, from
+normals estimated on the GPU over neighbourhoods of squared radius R2 (pc_error.estimate_normals_device).  Two more columns say which normals
+a row used: `normals` ('file' or 'estimated') and `normals_r2`.  D2 from estimated normals compares across our own rates and runs, not with
+published figures computed from a dataset's own normals.  The host metric has no estimator: it raises for such a cloud."""
 import os
 import time
 
@@ -45,10 +50,14 @@ def _timed(fn):
     return out, round(time.time() - t0, 3)
 
 
-def sweep(filedir, ckpts, outdir, scaling_factor=1.0, rho=1.0, res=1024, metric='host'):
-    """Yield one single-row DataFrame per checkpoint (columns as in the reference's results/*.csv).  metric: 'host' or 'device' (module doc)."""
+def sweep(filedir, ckpts, outdir, scaling_factor=1.0, rho=1.0, res=1024, metric='host', estimate_normals=None):
+    """Yield one single-row DataFrame per checkpoint (columns as in the reference's results/*.csv).  metric: 'host' or 'device',
+    estimate_normals: None or the squared radius R2 (module doc)."""
     if metric not in ('host', 'device'):
         raise ValueError(f"metric must be 'host' or 'device', got {metric!r}")
+    estimated = estimate_normals is not None and not ply_has_normals(filedir)
+    if estimated and metric != 'device':
+        raise ValueError(f"{filedir} has no normals (nx ny nz) and the host metric cannot estimate them: use metric='device'")
     x = load_sparse_tensor(filedir, device)
     os.makedirs(outdir, exist_ok=True)
     prefix = os.path.join(outdir, os.path.split(filedir)[-1].split('.')[0])
@@ -73,23 +82,30 @@ def sweep(filedir, ckpts, outdir, scaling_factor=1.0, rho=1.0, res=1024, metric=
         write_ply_ascii_geo(dec_ply, x_dec.C.detach().cpu().numpy()[:, 1:])
         if metric == 'device':
             b_dev = x_dec.C.detach().contiguous()
-            m = d2_psnr_device(a_dev, na_dev, b_dev, res) if with_normals else d1_psnr_device(a_dev, b_dev, res)
-            row = pd.DataFrame([{k: m[k] for k in (m if with_normals else D1_COLUMNS)}])
+            if estimated:
+                m = d2_psnr_device(a_dev, {'r2': estimate_normals}, b_dev, res)
+                row = pd.DataFrame([{k: m[k] for k in m if k not in ('normals_r2', 'normals_invalid')}])
+            else:
+                m = d2_psnr_device(a_dev, na_dev, b_dev, res) if with_normals else d1_psnr_device(a_dev, b_dev, res)
+                row = pd.DataFrame([{k: m[k] for k in (m if with_normals else D1_COLUMNS)}])
         else:
             row = pc_error(filedir, dec_ply, res=res, normal=with_normals, show=False)
         row["num_points(input)"], row["num_points(output)"], row["resolution"] = len(x), len(x_dec), res
         row["bits"], row["bpp"] = sum(bits).round(3), sum(bpps).round(3)
         row["bpp(coords)"], row["bpp(feats)"] = bpps[0], bpps[1]
         row["time(enc)"], row["time(dec)"] = t_enc, t_dec
+        if estimate_normals is not None:
+            row["normals"], row["normals_r2"] = ('estimated', int(estimate_normals)) if estimated else ('file', None)
         yield row
 
 
-def test(filedir, ckptdir_list, outdir, resultdir, scaling_factor=1.0, rho=1.0, res=1024, verbose=True, metric='host'):
-    """Reference entry point (test.py:13): runs the sweep, rewrites `<resultdir>/<cloud>.csv` after every rate.  metric: 'host' | 'device'."""
+def test(filedir, ckptdir_list, outdir, resultdir, scaling_factor=1.0, rho=1.0, res=1024, verbose=True, metric='host', estimate_normals=None):
+    """Reference entry point (test.py:13): runs the sweep, rewrites `<resultdir>/<cloud>.csv` after every rate.  metric: 'host' | 'device';
+    estimate_normals: None | R2 (module doc)."""
     os.makedirs(resultdir, exist_ok=True)
     csv_name = os.path.join(resultdir, os.path.split(filedir)[-1].split('.')[0] + '.csv')
     rows, table = [], None
-    for rate, row in enumerate(sweep(filedir, ckptdir_list, outdir, scaling_factor, rho, res, metric), start=1):
+    for rate, row in enumerate(sweep(filedir, ckptdir_list, outdir, scaling_factor, rho, res, metric, estimate_normals), start=1):
         rows.append(row)
         table = pd.concat(rows, ignore_index=True)
         table.to_csv(csv_name, index=False)
@@ -125,9 +141,12 @@ def main(argv=None):
     parser.add_argument("--ckpts", nargs='*', default=REFERENCE_CKPTS)
     parser.add_argument("--metric", choices=('host', 'device'), default='host',
                         help='where D1 / D2 are computed: host (pc_error on the PLY files, as the reference) or device (GPU)')
+    parser.add_argument("--estimate_normals", nargs='?', type=int, const=16, default=None, metavar='R2',
+                        help='with --metric device: D2 for a cloud without normals, from normals estimated on the GPU over neighbourhoods '
+                             'of squared radius R2 (1 .. 64, 16 when no value is given)')
     args = parser.parse_args(argv)
     table = test(args.filedir, args.ckpts, args.outdir, args.resultdir, scaling_factor=args.scaling_factor, rho=args.rho, res=args.res,
-                 metric=args.metric)
+                 metric=args.metric, estimate_normals=args.estimate_normals)
     name = os.path.split(args.filedir)[-1][:-4]
     try:
         plot_rd(table, name, os.path.join(args.resultdir, name + '.jpg'))
