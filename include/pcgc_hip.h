@@ -487,6 +487,26 @@ size_t pcgc_d2_reduce_workspace_bytes(void);
 int pcgc_d2_reduce(const int64_t* c2c, const double* c2p, int64_t n, int64_t* c2c_sum_max, double* c2p_sum, void* workspace, size_t workspace_bytes,
                    void* stream);
 
+/* ---- Per-point attributes (colours) between two clouds (csrc/colour.hip).  Tie sets are the kept ones of pcgc_d2_fill +
+ *      pcgc_d2_segment_lowest: seg [n+1], kept [n], rows.  Integer arithmetic throughout: exact, bitwise reproducible, independent of the
+ *      order of atomics and of the row order of the source (as long as no tie set exceeds its cap). */
+/* attr_t [nt,C] (uint8, C = 1 .. 4) from attr_s [ns,C]: (st) = tie sets of S in T, (ts) = tie sets of T in S.  R(t) = the sources whose tie
+ * set holds t; attr(t) = (2 sum + |R|) / (2 |R|) per channel over R(t) (the mean rounded half up), over t's own tie set when R(t) is empty.
+ * Accumulators are 32-bit fields: ns above 16 843 009 (255 ns >= 2^32) is refused with -2, never wrapped; C outside 1 .. 4 is -2. */
+size_t pcgc_attr_transfer_workspace_bytes(int64_t ns, int64_t nt, int channels);
+int pcgc_attr_transfer(const int64_t* seg_st, const int32_t* kept_st, const int32_t* rows_st, int64_t ns, const int64_t* seg_ts,
+                       const int32_t* kept_ts, const int32_t* rows_ts, int64_t nt, const uint8_t* attr_s, int channels, uint8_t* attr_t,
+                       void* workspace, size_t workspace_bytes, void* stream);
+/* per point i of P (colours cp uint8 [n,3]) against the rounded mean colour of its kept tie set in Q (cq uint8 [nq,3]), d = own - mean:
+ * yuv2 [n,3] (int64) = (2126 dr + 7152 dg + 722 db)^2, (-1146 dr - 3854 dg + 5000 db)^2, (5000 dr - 4542 dg - 458 db)^2 — the squared BT.709
+ * differences times (255 * 10^4)^2; rgb2 [n,3] (int32) = dr^2, dg^2, db^2 */
+int pcgc_colour_dist(const uint8_t* cp, int64_t n, const uint8_t* cq, int64_t nq, const int64_t* seg, const int32_t* kept, const int32_t* rows,
+                     int64_t* yuv2, int32_t* rgb2, void* stream);
+/* out [9] (int64): sums over i of the low 32 bits of yuv2[i][k] (k = 0..2), of the high 32 bits (3..5): total_k = out[3+k] * 2^32 + out[k],
+ * exact for n < 2^31; maxima of rgb2[i][k] (6..8).  The grid is a function of n only. */
+size_t pcgc_colour_reduce_workspace_bytes(void);
+int pcgc_colour_reduce(const int64_t* yuv2, const int32_t* rgb2, int64_t n, int64_t* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Estimated surface normals of a voxelised cloud (csrc/normals.hip; nothing in the reference: its D2 figures assume clouds whose normals
  *      another tool estimated).  Per row at voxel p: the neighbourhood is every DISTINCT voxel q of the row's batch with |q - p|^2 <= r2 (p
  *      included); moments [n,10] = k, sum dx dy dz, sum dx^2 dy^2 dz^2 dxdy dxdz dydz over d = q - p (exact); S = k sum(d d^T) - (sum d)(sum d)^T;
@@ -515,6 +535,8 @@ int pcgc_set_normals_mapping(int mode);
  *      reference (a line is data iff all its ' '-separated tokens parse as floats); columns 0:3 truncated to int. ---- */
 int64_t pcgc_ply_read_ascii_geo(const char* path, int32_t* xyz /*[host cap,3] or NULL*/, int64_t cap);
 int pcgc_ply_write_ascii_geo(const char* path, const int32_t* xyz /*[host n,3]*/, int64_t n);
+/* the same with `property uchar red / green / blue` after the coordinates, integer text */
+int pcgc_ply_write_ascii_geo_rgb(const char* path, const int32_t* xyz /*[host n,3]*/, const uint8_t* rgb /*[host n,3]*/, int64_t n);
 
 /* ---- the bitstream files of several items at once (HOST; native threads): the host half of Coder.encode / Coder.decode
  *      (coder.py:49-55,85-87,93-100) for the items of a collated batch or for one cloud.  stems[i] = "<prefix><postfix>" of item i;

@@ -114,6 +114,11 @@ SIGNATURES = {
     'pcgc_d2_c2p': (ci, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
     'pcgc_d2_reduce_workspace_bytes': (sz, []),
     'pcgc_d2_reduce': (ci, [vp, vp, i64, vp, vp, vp, sz, vp]),
+    'pcgc_attr_transfer_workspace_bytes': (sz, [i64, i64, ci]),
+    'pcgc_attr_transfer': (ci, [vp, vp, vp, i64, vp, vp, vp, i64, vp, ci, vp, vp, sz, vp]),
+    'pcgc_colour_dist': (ci, [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp]),
+    'pcgc_colour_reduce_workspace_bytes': (sz, []),
+    'pcgc_colour_reduce': (ci, [vp, vp, i64, vp, vp, sz, vp]),
     'pcgc_normals_ball_masks': (i64, [i32, vp]),
     'pcgc_normals_workspace_bytes': (sz, [i64]),
     'pcgc_normals_estimate': (ci, [vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, i32, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
@@ -143,6 +148,7 @@ SIGNATURES = {
     'pcgc_crc32': (C.c_uint32, [C.c_uint32, vp, i64]),
     'pcgc_ply_read_ascii_geo': (i64, [C.c_char_p, vp, i64]),
     'pcgc_ply_write_ascii_geo': (ci, [C.c_char_p, vp, i64]),
+    'pcgc_ply_write_ascii_geo_rgb': (ci, [C.c_char_p, vp, vp, i64]),
     'pcgc_mesh_read': (ci, [C.c_char_p, vp, i64, vp, i64, vp]),
     'pcgc_mesh_cdf_workspace_bytes': (sz, [i64]),
     'pcgc_mesh_area_cdf': (ci, [vp, i64, vp, i64, vp, vp, vp, sz, vp]),

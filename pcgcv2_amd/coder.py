@@ -18,7 +18,7 @@ import torch
 
 from . import gpcc, ops
 from .data_utils import (array2vector, istopk, sort_spare_tensor, load_sparse_tensor, scale_sparse_tensor,  # noqa: F401
-                         write_ply_ascii_geo, read_ply_ascii_geo)
+                         write_ply_ascii_geo, write_ply_ascii_geo_rgb, read_ply_ascii_geo)
 from .pc_error import pc_error
 from .pcc_model import PCCModel
 from .sparse import SparseTensor, CoordMap, require_gpu
@@ -624,6 +624,9 @@ def _parse_cli(argv):
     p.add_argument("--rho", type=float, default=1.0, help='the ratio of the number of output points to the number of input points')
     p.add_argument("--res", type=int, default=1024, help='resolution')
     p.add_argument("--outdir", default='./output')
+    p.add_argument("--recolour", action='store_true',
+                   help="carry the colours (red green blue) of --filedir onto the decoded cloud: _dec.ply is written with them and the colour "
+                        "PSNR of the geometry loss is printed")
     return p.parse_args(argv)
 
 
@@ -639,6 +642,21 @@ class _Stopwatch:
         if self.sync and torch.cuda.is_available():
             torch.cuda.synchronize()
         print(f'{self.label}:\t', round(time.time() - self.t0, self.digits), 's')
+
+
+def _recolour(filedir, x_dec):
+    """colours of the decoded cloud carried from the file's raw rows (duplicates included, as the device metric reads them), and the colour
+    columns of the pair -> (uint8 [n,3] device tensor, dict)"""
+    from .data_utils import read_ply_ascii_with_colours
+    from .pc_error import colour_psnr_device, lattice_coords, nn_both, recolour_device
+    xyz, rgb = read_ply_ascii_with_colours(filedir)
+    if rgb is None:
+        raise ValueError(f'{filedir} has no colours (red green blue): --recolour needs them')
+    b = x_dec.C.detach().contiguous()
+    a, ca = lattice_coords(xyz, b.device), torch.from_numpy(rgb).to(b.device)
+    nn = nn_both(a, b)
+    cb = recolour_device(a, ca, b, nn=nn)
+    return cb, colour_psnr_device(a, ca, b, cb, nn=nn)
 
 
 def main(argv=None):
@@ -671,11 +689,19 @@ def main(argv=None):
     print('bits:\t', bits, '\nbpps:\t', bpps)
     print('bits:\t', sum(bits), '\nbpps:\t', sum(bpps).round(3))
 
+    if args.recolour:
+        with _Stopwatch('Recolour Time'):
+            rgb_dec, colour = _recolour(args.filedir, x_dec)
     with _Stopwatch('Write PC Time', sync=False):
-        write_ply_ascii_geo(prefix + '_dec.ply', x_dec.C.detach().cpu().numpy()[:, 1:])
+        if args.recolour:
+            write_ply_ascii_geo_rgb(prefix + '_dec.ply', x_dec.C.detach().cpu().numpy()[:, 1:], rgb_dec.cpu().numpy())
+        else:
+            write_ply_ascii_geo(prefix + '_dec.ply', x_dec.C.detach().cpu().numpy()[:, 1:])
     with _Stopwatch('PC Error Metric Time', sync=False):
         metrics = pc_error(args.filedir, prefix + '_dec.ply', res=args.res, show=False)
     print('D1 PSNR:\t', metrics["mseF,PSNR (p2point)"][0])
+    if args.recolour:
+        print('Colour PSNR (Y):\t', colour['c[0],PSNRF'])
 
 
 if __name__ == '__main__':

@@ -107,3 +107,28 @@ extern "C" int pcgc_ply_write_ascii_geo(const char* path, const int32_t* xyz, in
     std::fclose(f);
     return ok ? 0 : -1;
 }
+
+// The same file with `property uchar red / green / blue` after the coordinates (integer text): what mpeg-pcc-dmetric reads with `-c 1`, and
+// pcgc_ply_read_ascii_geo reads its first three columns.
+extern "C" int pcgc_ply_write_ascii_geo_rgb(const char* path, const int32_t* xyz, const uint8_t* rgb, int64_t n) {
+    FILE* f = std::fopen(path, "wb");
+    if (!f) return -1;
+    std::vector<char> out; out.reserve((size_t)n * 28 + 384);
+    char head[384];
+    int h = std::snprintf(head, sizeof(head), "ply\nformat ascii 1.0\nelement vertex %lld\nproperty float x\nproperty float y\nproperty float z\n"
+                          "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n", (long long)n);
+    out.insert(out.end(), head, head + h);
+    char tmp[16];
+    auto put_int = [&](int32_t v) {
+        int64_t a = v; if (a < 0) { out.push_back('-'); a = -a; }
+        int k = 0; do { tmp[k++] = (char)('0' + a % 10); a /= 10; } while (a);
+        while (k) out.push_back(tmp[--k]);
+    };
+    for (int64_t i = 0; i < n; ++i) {
+        for (int c = 0; c < 3; ++c) { put_int(xyz[3 * i + c]); out.push_back(' '); }
+        put_int(rgb[3 * i]); out.push_back(' '); put_int(rgb[3 * i + 1]); out.push_back(' '); put_int(rgb[3 * i + 2]); out.push_back('\n');
+    }
+    const bool ok = std::fwrite(out.data(), 1, out.size(), f) == out.size();
+    std::fclose(f);
+    return ok ? 0 : -1;
+}

@@ -51,6 +51,71 @@ def write_ply_ascii_geo_normals(filedir, coords, normals):
         frame.to_csv(f, sep=' ', header=False, index=False, float_format='%.9g', lineterminator='\n')
 
 
+_RGB = ('red', 'green', 'blue')
+
+
+def _ply_vertex_header(path):
+    """-> (names of the vertex properties in file order, vertex count, number of header lines) of an ASCII PLY"""
+    names, n, skip = [], 0, 0
+    with open(path, 'rb') as f:
+        in_vertex = False
+        for line in f:
+            skip += 1
+            t = line.decode('ascii', 'replace').split()
+            if not t:
+                continue
+            if t[0] == 'element':
+                in_vertex = t[1] == 'vertex'
+                if in_vertex:
+                    n = int(t[2])
+            elif t[0] == 'property' and in_vertex:
+                names.append(t[-1])
+            elif t[0] == 'end_header':
+                break
+    return names, n, skip
+
+
+def ply_has_colours(path):
+    """True iff the ASCII PLY's vertex element declares red, green and blue (header scan only)"""
+    try:
+        names = _ply_vertex_header(path)[0]
+    except OSError:
+        return False
+    return all(c in names for c in _RGB)
+
+
+def read_ply_ascii_with_colours(path):
+    """ASCII PLY -> (coordinates float64 [n,3], colours uint8 [n,3] or None): the vertex properties x y z and, when present, red green
+    blue, wherever they sit among the columns"""
+    import pandas as pd
+    names, n, skip = _ply_vertex_header(path)
+    if not all(c in names for c in 'xyz'):
+        raise ValueError(f'{path}: no x / y / z vertex properties')
+    data = pd.read_csv(path, sep=r'\s+', header=None, skiprows=skip, nrows=n, dtype=np.float64, engine='c').to_numpy()
+    xyz = np.ascontiguousarray(data[:, [names.index(c) for c in 'xyz']])
+    if not all(c in names for c in _RGB):
+        return xyz, None
+    rgb = data[:, [names.index(c) for c in _RGB]]
+    if rgb.size and (rgb.min() < 0 or rgb.max() > 255 or not np.array_equal(rgb, np.rint(rgb))):
+        raise ValueError(f'{path}: red / green / blue are not 8-bit integers')
+    return xyz, np.ascontiguousarray(rgb.astype(np.uint8))
+
+
+def write_ply_ascii_geo_rgb(filedir, coords, rgb):
+    """ASCII PLY with `property float x/y/z` and `property uchar red/green/blue`, integer text (native writer): what mpeg-pcc-dmetric's
+    `-c 1` and read_ply_ascii_with_colours read; read_ply_ascii_geo reads its coordinates."""
+    from ._lib import lib, PcgcError
+    coords = np.ascontiguousarray(np.asarray(coords).astype('int'), dtype=np.int32).reshape(-1, 3)
+    rgb = np.asarray(rgb)
+    if rgb.dtype != np.uint8:
+        raise ValueError(f'write_ply_ascii_geo_rgb: colours must be uint8, got {rgb.dtype}')
+    rgb = np.ascontiguousarray(rgb).reshape(-1, 3)
+    if len(rgb) != len(coords):
+        raise ValueError(f'{len(coords)} points but {len(rgb)} colours')
+    if int(lib().pcgc_ply_write_ascii_geo_rgb(os.fsencode(filedir), coords.ctypes.data, rgb.ctypes.data, len(coords))) != 0:
+        raise PcgcError(f'cannot write {filedir}')
+
+
 def _h5py():
     try:
         import h5py

@@ -1813,6 +1813,72 @@ def d2_reduce(c2c, c2p):
     return sm, s
 
 
+# ------------------------------------------------------------------------------------------------ colours (csrc/colour.hip)
+ATTR_MAX_CHANNELS = 4
+ATTR_MAX_SOURCES = 0xFFFFFFFF // 255          # the accumulator fields are 32 bits wide: 255 * ns has to fit (pcgc_attr_transfer)
+
+
+def _u8(t, what):
+    if t.dtype != torch.uint8:
+        raise ValueError(f'{what}: expected uint8, got {t.dtype}')
+    if not t.is_cuda:
+        raise PcgcError(f'{what}: expected a device tensor')
+    return t.contiguous()
+
+
+def attr_transfer(nt, st, attr_s, ts):
+    """Attributes of cloud T (nt rows) from those of S (attr_s: uint8 [ns,C] device, C = 1 .. 4): st = d2_nn(S, T), ts = d2_nn(T, S).
+    A target takes the mean, rounded half up, over the sources whose tie set holds it, or — none does — over its own tie set in S.
+    Exact and bitwise reproducible (integer sums).  -> uint8 [nt,C]"""
+    _, seg, kept, rows = st
+    _, seg_ts, kept_ts, rows_ts = ts
+    attr_s = _u8(attr_s, 'attr_transfer: attributes')
+    if attr_s.dim() != 2 or not 1 <= attr_s.shape[1] <= ATTR_MAX_CHANNELS:
+        raise ValueError(f'attr_transfer: attributes must be [ns,C] with C in 1 .. {ATTR_MAX_CHANNELS}, got {tuple(attr_s.shape)}')
+    ns, C = attr_s.shape
+    if kept.shape[0] != ns or kept_ts.shape[0] != nt:
+        raise ValueError(f'attr_transfer: {ns} source rows and {nt} target rows, but the tie sets are of {kept.shape[0]} and {kept_ts.shape[0]}')
+    if ns == 0 or nt == 0:
+        raise ValueError('attr_transfer: empty point cloud')
+    dev = attr_s.device
+    out = torch.empty((nt, C), dtype=torch.uint8, device=dev)
+    ws_bytes = int(lib().pcgc_attr_transfer_workspace_bytes(ns, nt, C))
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    check(lib().pcgc_attr_transfer(_p(seg), _p(kept), _p(rows), ns, _p(seg_ts), _p(kept_ts), _p(rows_ts), nt, _p(attr_s), C, _p(out), _p(ws),
+                                   ws_bytes, _stream(attr_s)), 'attr_transfer')
+    return out
+
+
+def colour_dist(cp, cq, nn):
+    """Per point of P (cp: uint8 [np,3] device) against the rounded mean colour of its tie set nn = d2_nn(P, Q) in Q (cq: uint8 [nq,3]):
+    -> (yuv2 int64 [np,3], rgb2 int32 [np,3]), the squared BT.709 differences times (255 * 10^4)^2 and the squared RGB differences."""
+    _, seg, kept, rows = nn
+    cp, cq = _u8(cp, 'colour_dist: colours'), _u8(cq, 'colour_dist: colours')
+    for c in (cp, cq):
+        if c.dim() != 2 or c.shape[1] != 3:
+            raise ValueError(f'colour_dist: colours must be [n,3], got {tuple(c.shape)}')
+    n = cp.shape[0]
+    if kept.shape[0] != n:
+        raise ValueError(f'colour_dist: {n} colours but tie sets of {kept.shape[0]} points')
+    if n == 0 or cq.shape[0] == 0:
+        raise ValueError('colour_dist: empty point cloud')
+    yuv2 = torch.empty((n, 3), dtype=torch.int64, device=cp.device)
+    rgb2 = torch.empty((n, 3), dtype=torch.int32, device=cp.device)
+    check(lib().pcgc_colour_dist(_p(cp), n, _p(cq), cq.shape[0], _p(seg), _p(kept), _p(rows), _p(yuv2), _p(rgb2), _stream(cp)), 'colour_dist')
+    return yuv2, rgb2
+
+
+def colour_reduce(yuv2, rgb2):
+    """-> int64 [9] device: low-word sums and high-word sums of yuv2's three columns (total_k = out[3+k] * 2**32 + out[k], exact), maxima of
+    rgb2's three columns"""
+    n, dev = yuv2.shape[0], yuv2.device
+    out = torch.empty(9, dtype=torch.int64, device=dev)
+    ws_bytes = int(lib().pcgc_colour_reduce_workspace_bytes())
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    check(lib().pcgc_colour_reduce(_p(yuv2), _p(rgb2), n, _p(out), _p(ws), ws_bytes, _stream(yuv2)), 'colour_reduce')
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ estimated normals (csrc/normals.hip)
 NORMALS_MAX_R2 = 64
 _NORMALS_BALL = {}

@@ -14,7 +14,12 @@ read and uploaded once, the decoded cloud is taken from the decoder's tensor dir
 estimate_normals=R2 (`--estimate_normals [R2]`, off by default; metric='device' only): a cloud WITHOUT normals gets the D2 columns too, from
 normals estimated on the GPU over neighbourhoods of squared radius R2 (pc_error.estimate_normals_device).  Two more columns say which normals
 a row used: `normals` ('file' or 'estimated') and `normals_r2`.  D2 from estimated normals compares across our own rates and runs, not with
-published figures computed from a dataset's own normals.  The host metric has no estimator: it raises for such a cloud."""
+published figures computed from a dataset's own normals.  The host metric has no estimator: it raises for such a cloud.
+
+colour=True (`--colour`, off by default): the input's colours (red green blue) are carried onto every decoded cloud (pc_error.recolour_device
+with metric='device', sharing the two nearest-neighbour searches with D2; pc_error.recolour with metric='host'), `_dec.ply` is written with
+them, and the row gains the 36 colour columns of `pc_error_d -c 1` (pc_error.COLOUR_COLUMNS) — the colour distortion the geometry loss
+induces.  The columns are the same both ways.  An input without colours raises ValueError."""
 import os
 import time
 
@@ -23,9 +28,10 @@ import pandas as pd
 import torch
 
 from .coder import Coder, stream_bits
-from .data_utils import load_sparse_tensor, scale_sparse_tensor, write_ply_ascii_geo
-from .pc_error import (D1_COLUMNS, d1_psnr_device, d2_psnr_device, lattice_coords, pc_error, ply_has_normals,
-                       read_ply_ascii_with_normals)
+from .data_utils import (load_sparse_tensor, ply_has_colours, read_ply_ascii_with_colours, scale_sparse_tensor, write_ply_ascii_geo,
+                         write_ply_ascii_geo_rgb)
+from .pc_error import (COLOUR_COLUMNS, D1_COLUMNS, colour_psnr_device, d1_psnr_device, d2_psnr_device, lattice_coords, nn_both, pc_error,
+                       ply_has_normals, read_ply_ascii_with_normals, recolour, recolour_device)
 from .pcc_model import PCCModel
 
 device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
@@ -50,11 +56,13 @@ def _timed(fn):
     return out, round(time.time() - t0, 3)
 
 
-def sweep(filedir, ckpts, outdir, scaling_factor=1.0, rho=1.0, res=1024, metric='host', estimate_normals=None):
+def sweep(filedir, ckpts, outdir, scaling_factor=1.0, rho=1.0, res=1024, metric='host', estimate_normals=None, colour=False):
     """Yield one single-row DataFrame per checkpoint (columns as in the reference's results/*.csv).  metric: 'host' or 'device',
-    estimate_normals: None or the squared radius R2 (module doc)."""
+    estimate_normals: None or the squared radius R2, colour: carry the input's colours and report their distortion (module doc)."""
     if metric not in ('host', 'device'):
         raise ValueError(f"metric must be 'host' or 'device', got {metric!r}")
+    if colour and not ply_has_colours(filedir):
+        raise ValueError(f'{filedir} has no colours (red green blue): colour=True needs them')
     estimated = estimate_normals is not None and not ply_has_normals(filedir)
     if estimated and metric != 'device':
         raise ValueError(f"{filedir} has no normals (nx ny nz) and the host metric cannot estimate them: use metric='device'")
@@ -68,6 +76,9 @@ def sweep(filedir, ckpts, outdir, scaling_factor=1.0, rho=1.0, res=1024, metric=
         a_xyz, a_nrm = read_ply_ascii_with_normals(filedir)
         a_dev = lattice_coords(a_xyz, device)
         na_dev = torch.from_numpy(a_nrm).to(device) if with_normals else None
+    if colour:                                    # the raw rows again, with their colours (duplicates included, as the metric reads them)
+        c_xyz, c_rgb = read_ply_ascii_with_colours(filedir)
+        ca_dev = torch.from_numpy(c_rgb).to(device) if metric == 'device' else None
     for rate, ckpt in enumerate(ckpts, start=1):
         model.load_state_dict(_state_dict(ckpt))
         coder = Coder(model=model, filename=prefix)
@@ -79,17 +90,28 @@ def sweep(filedir, ckpts, outdir, scaling_factor=1.0, rho=1.0, res=1024, metric=
         bits = stream_bits(prefix, tag)
         bpps = (bits / len(x)).round(3)
         dec_ply = prefix + tag + '_dec.ply'
-        write_ply_ascii_geo(dec_ply, x_dec.C.detach().cpu().numpy()[:, 1:])
+        dec_xyz = x_dec.C.detach().cpu().numpy()[:, 1:]
+        if not colour:
+            write_ply_ascii_geo(dec_ply, dec_xyz)
         if metric == 'device':
             b_dev = x_dec.C.detach().contiguous()
+            nn = nn_both(a_dev, b_dev) if colour else None          # both searches once: D2, the recolouring and the colour metric read them
             if estimated:
-                m = d2_psnr_device(a_dev, {'r2': estimate_normals}, b_dev, res)
+                m = d2_psnr_device(a_dev, {'r2': estimate_normals}, b_dev, res, nn=nn)
                 row = pd.DataFrame([{k: m[k] for k in m if k not in ('normals_r2', 'normals_invalid')}])
             else:
-                m = d2_psnr_device(a_dev, na_dev, b_dev, res) if with_normals else d1_psnr_device(a_dev, b_dev, res)
+                m = d2_psnr_device(a_dev, na_dev, b_dev, res, nn=nn) if with_normals else d1_psnr_device(a_dev, b_dev, res)
                 row = pd.DataFrame([{k: m[k] for k in (m if with_normals else D1_COLUMNS)}])
+            if colour:
+                cb_dev = recolour_device(a_dev, ca_dev, b_dev, nn=nn)
+                write_ply_ascii_geo_rgb(dec_ply, dec_xyz, cb_dev.cpu().numpy())
+                mc = colour_psnr_device(a_dev, ca_dev, b_dev, cb_dev, nn=nn)
+                for k in COLOUR_COLUMNS:
+                    row[k] = mc[k]
         else:
-            row = pc_error(filedir, dec_ply, res=res, normal=with_normals, show=False)
+            if colour:
+                write_ply_ascii_geo_rgb(dec_ply, dec_xyz, recolour(c_xyz, c_rgb, dec_xyz))
+            row = pc_error(filedir, dec_ply, res=res, normal=with_normals, show=False, **({'color': True} if colour else {}))
         row["num_points(input)"], row["num_points(output)"], row["resolution"] = len(x), len(x_dec), res
         row["bits"], row["bpp"] = sum(bits).round(3), sum(bpps).round(3)
         row["bpp(coords)"], row["bpp(feats)"] = bpps[0], bpps[1]
@@ -99,13 +121,14 @@ def sweep(filedir, ckpts, outdir, scaling_factor=1.0, rho=1.0, res=1024, metric=
         yield row
 
 
-def test(filedir, ckptdir_list, outdir, resultdir, scaling_factor=1.0, rho=1.0, res=1024, verbose=True, metric='host', estimate_normals=None):
+def test(filedir, ckptdir_list, outdir, resultdir, scaling_factor=1.0, rho=1.0, res=1024, verbose=True, metric='host', estimate_normals=None,
+         colour=False):
     """Reference entry point (test.py:13): runs the sweep, rewrites `<resultdir>/<cloud>.csv` after every rate.  metric: 'host' | 'device';
-    estimate_normals: None | R2 (module doc)."""
+    estimate_normals: None | R2; colour: False | True (module doc)."""
     os.makedirs(resultdir, exist_ok=True)
     csv_name = os.path.join(resultdir, os.path.split(filedir)[-1].split('.')[0] + '.csv')
     rows, table = [], None
-    for rate, row in enumerate(sweep(filedir, ckptdir_list, outdir, scaling_factor, rho, res, metric, estimate_normals), start=1):
+    for rate, row in enumerate(sweep(filedir, ckptdir_list, outdir, scaling_factor, rho, res, metric, estimate_normals, colour), start=1):
         rows.append(row)
         table = pd.concat(rows, ignore_index=True)
         table.to_csv(csv_name, index=False)
@@ -144,9 +167,11 @@ def main(argv=None):
     parser.add_argument("--estimate_normals", nargs='?', type=int, const=16, default=None, metavar='R2',
                         help='with --metric device: D2 for a cloud without normals, from normals estimated on the GPU over neighbourhoods '
                              'of squared radius R2 (1 .. 64, 16 when no value is given)')
+    parser.add_argument("--colour", action='store_true',
+                        help='carry the colours of the input onto every decoded cloud (written into _dec.ply) and report their distortion')
     args = parser.parse_args(argv)
     table = test(args.filedir, args.ckpts, args.outdir, args.resultdir, scaling_factor=args.scaling_factor, rho=args.rho, res=args.res,
-                 metric=args.metric, estimate_normals=args.estimate_normals)
+                 metric=args.metric, estimate_normals=args.estimate_normals, colour=args.colour)
     name = os.path.split(args.filedir)[-1][:-4]
     try:
         plot_rd(table, name, os.path.join(args.resultdir, name + '.jpg'))
