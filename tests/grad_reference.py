@@ -86,6 +86,21 @@ def eb_gradients(params, y, bound=1e-9, passthrough=False):
     return gy.numpy(), gp.numpy(), float(b.detach())
 
 
+def eb_row_gradients(params, y, bound=1e-9):
+    """d (row i's rate) / d params -> [n, 44 C] in the packing of `params`, in ONE backward pass: element (i, c) uses the 44 parameters of
+    channel c only, so every element is evaluated as a channel of its own (n C channels, one row) holding a copy of its channel's
+    parameters, and the gradient with respect to the copies is the Jacobian of the per-row rates with respect to the parameters."""
+    y = np.asarray(y, np.float64)
+    n, C = y.shape
+    if n == 0:
+        return np.zeros((0, 44 * C))
+    p = torch.as_tensor(np.asarray(params, np.float64))
+    idx = torch.arange(n * C) % C
+    big = torch.cat([t[idx].reshape(-1) for t in eb_unpack(p, C)])
+    _, g, _ = eb_gradients(big.numpy(), y.reshape(1, n * C), bound)
+    return np.concatenate([t.reshape(n, -1).numpy() for t in eb_unpack(torch.from_numpy(g), n * C)], 1)
+
+
 def bce_gradient(logits, mask, ln2=LN2):
     x = torch.tensor(np.asarray(logits, np.float64).ravel(), requires_grad=True)
     g, = torch.autograd.grad(bce_bits(x, mask, ln2), [x])
