@@ -6,7 +6,7 @@ the channel concat are written by the producing kernel (ME.cat / MinkowskiReLU /
 extra HBM round trip)."""
 import torch
 
-from . import dispatch, ops
+from . import derived, dispatch, ops
 from .nn import MinkowskiConvolution as Conv, MinkowskiGenerativeConvolutionTranspose as UpConv, MinkowskiPruning
 from .sparse import CoordMap, SparseTensor
 
@@ -53,12 +53,15 @@ class InceptionResNet(torch.nn.Module):
         return SparseTensor(out, coordinate_map=x.cmap)
 
     def _tables(self, kind, build, params):
-        """derived weight tables of one kind, rebuilt whenever a parameter tensor was replaced or modified"""
-        stamp = tuple((p.data_ptr(), p._version) for p in params)
-        cache = self.__dict__.setdefault('_derived', {})
-        if cache.get(kind, (None, None))[0] != stamp:
-            cache[kind] = (stamp, build(params))
-        return cache[kind][1]
+        """derived weight tables of one kind, rebuilt whenever a parameter tensor was replaced or modified (derived.py)"""
+        return derived.fetch(self.__dict__.setdefault('_derived', {}), kind, params, lambda: build(params))
+
+    def _drop_derived(self):
+        self.__dict__.pop('_derived', None)
+
+    def weights_changed(self):
+        """after a write through `.data`: drop the derived tables of the block and of its five convs (derived.weights_changed)"""
+        derived.weights_changed(self)
 
 
 def make_layer(block, block_layers, channels):

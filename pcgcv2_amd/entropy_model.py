@@ -29,7 +29,7 @@ import torch
 import torch.nn as nn
 from torch.nn.parameter import Parameter
 
-from . import ops
+from . import derived, ops
 from ._lib import PcgcError
 
 
@@ -81,7 +81,7 @@ class EntropyBottleneck(nn.Module):
         # the reference's accidental aliases of the LAST layer's tensors (same Parameter objects)
         self.matrix, self.bias, self.factor = self._matrices[-1], self._biases[-1], self._factors[-1]
         self.table_mode = 'reference'
-        self._packed = self._packed_stamp = None
+        self._packed = None
         self._host = self._host_stamp = None
         _MODELS.add(self)                                    # (table_cache(clear=True) reaches every live model's cache)
 
@@ -89,23 +89,49 @@ class EntropyBottleneck(nn.Module):
         """coder.py:44 calls `entropy_model.cpu()`; the tables are evaluated on the GPU here, so the module stays put."""
         return self
 
+    def _params12(self):
+        return [p for lst in (self._matrices, self._biases, self._factors) for p in lst._parameters.values()]
+
     def _stamp(self):
-        """identity + version of the 12 parameter tensors: any in-place update, re-assignment, .to() or load_state_dict —
-        through this module or any parent container — changes it, so derived copies can never go stale."""
-        return tuple((p.data_ptr(), p._version, p.device) for lst in (self._matrices, self._biases, self._factors)
-                     for p in lst._parameters.values())
+        """identity + version of the 12 parameter tensors (derived.stamp): any in-place update, re-assignment, .to() or load_state_dict —
+        through this module or any parent container — changes it.  The first call that sees a new stamp drops every derived copy and
+        takes aliases of the 12 tensors: while a stamp is current the storages it names stay allocated, so no later tensor can show the
+        same (address, version) pair, and nothing cached under an earlier stamp survives to be matched by one.  Writes through `.data`
+        change no stamp: `weights_changed()` after them (cache contract)."""
+        params = self._params12()
+        s = derived.stamp(params, device=True)
+        if s != self.__dict__.get('_seen_stamp'):
+            with _TABLE_LOCK:
+                if s != self.__dict__.get('_seen_stamp'):
+                    self.invalidate()
+                    self.__dict__['_aliases'] = tuple(p.detach() for p in params)
+                    self.__dict__['_seen_stamp'] = s
+        return s
 
     def packed_params(self, device):
-        """352 fp32: matrices 0..3 | biases 0..3 | factors 0..3 — the layout pcgc_cdf_table expects."""
-        stamp = (self._stamp(), device)
-        if self._packed is None or self._packed_stamp != stamp:
+        """352 fp32: matrices 0..3 | biases 0..3 | factors 0..3 — the layout pcgc_cdf_table expects.  Built on the caller's stream and
+        published with an event: a caller on another stream waits for the build (derived.publish / order)."""
+        stamp = (self._stamp(), str(device))
+        e = self._packed
+        if e is None or e.stamp != stamp:
             parts = [p.detach().reshape(-1).float() for lst in (self._matrices, self._biases, self._factors) for p in lst]
-            self._packed, self._packed_stamp = torch.cat(parts).to(device).contiguous(), stamp
-        return self._packed
+            e = self._packed = derived.publish(stamp, (), lambda: torch.cat(parts).to(device).contiguous(), device=device)
+        elif e.event is not None:
+            derived.order(e)
+        return e.value
 
     def invalidate(self):
         self._packed = self._host = self._hpacked = None
         self.__dict__.pop('_table_cache', None)
+
+    def _drop_derived(self):
+        with _TABLE_LOCK:
+            self.invalidate()
+            self.__dict__.pop('_seen_stamp', None)
+
+    def weights_changed(self):
+        """after a write through `.data`: drop the packed copies and the cached tables (derived.weights_changed)"""
+        derived.weights_changed(self)
 
     def _host_params(self):
         """fp32 CPU copies of (matrices, biases, factors), refreshed when the parameters change."""
@@ -220,9 +246,11 @@ class EntropyBottleneck(nn.Module):
             hit = (table, zlib.crc32(table.tobytes()))
             if TABLE_CACHE:
                 with _TABLE_LOCK:
+                    cache = self.__dict__.setdefault('_table_cache', {})         # (a weight change in between has dropped the old dict)
                     while len(cache) >= self.TABLE_CACHE_SIZE:
                         cache.pop(next(iter(cache)), None)                       # (dicts keep insertion order: drop the oldest)
-                    cache[key] = hit
+                    if key[0] == self.__dict__.get('_seen_stamp'):               # (never file a table under a stamp that is no longer current)
+                        cache[key] = hit
         return hit if want_crc else hit[0]
 
     def _quantize(self, inputs, mode, generator=None):

@@ -4,7 +4,7 @@ checkpoints (`torch.load(p)['model']`, coder.py:141-142) load with a strict load
 import math
 import torch
 
-from . import dispatch, ops
+from . import derived, dispatch, ops
 from .sparse import SparseTensor
 
 
@@ -23,6 +23,13 @@ class _ConvBase(torch.nn.Module):
             self.kernel.uniform_(-bound, bound)
             if self.bias is not None:
                 self.bias.zero_()
+
+    def _drop_derived(self):
+        self.__dict__.pop('_child_tables', None)
+
+    def weights_changed(self):
+        """after a write through `.data`: drop the derived tables, if the layer keeps any (derived.weights_changed)"""
+        derived.weights_changed(self)
 
     def extra_repr(self):
         return f'in={self.in_channels}, out={self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}'
@@ -84,14 +91,11 @@ class MinkowskiConvolution(_ConvBase):
         return SparseTensor(y, coordinate_map=cmap)
 
     def _table(self, build):
-        """the layer's kernel re-laid-out as MFMA B fragments, rebuilt whenever the parameter tensor was replaced or modified; one slot per
-        layout (a head whose level sizes straddle a dispatch gate alternates between two layouts: neither evicts the other)"""
-        stamp = (self.kernel.data_ptr(), self.kernel._version)
-        slots = self.__dict__.setdefault('_child_tables', {})
-        hit = slots.get(build.__name__)
-        if hit is None or hit[0] != stamp:
-            hit = slots[build.__name__] = (stamp, build(self.kernel))
-        return hit[1]
+        """the layer's kernel re-laid-out as MFMA B fragments, rebuilt whenever the parameter tensor was replaced or modified (derived.py:
+        the entry pins the tensor it was built from and is ordered after its build on every stream); one slot per layout (a head whose
+        level sizes straddle a dispatch gate alternates between two layouts: neither evicts the other)"""
+        kernel = self.kernel
+        return derived.fetch(self.__dict__.setdefault('_child_tables', {}), build.__name__, (kernel,), lambda: build(kernel))
 
 
 class MinkowskiGenerativeConvolutionTranspose(_ConvBase):

@@ -688,12 +688,8 @@ def _rows_irn32_index():
 def rows_irn32_tables(params):
     """(table A 54 KB, table B 27.5 KB) of the plain-level C = 32 InceptionResNet passes; params as in irn_block."""
     W00, b00, W01, b01, W10, b10, W11, b11, W12, b12 = params
-    key = ('rows_irn32', W00.device)
-    if key not in _TABLE_INDEX:
-        ia, ib = _rows_irn32_index()
-        _TABLE_INDEX[key] = (torch.from_numpy(ia).to(W00.device), torch.from_numpy(ib).to(W00.device))
+    ia, ib = _table_index(('rows_irn32', W00.device), _rows_irn32_index)
     flat = torch.cat([w.detach().reshape(-1) for w in (W00, W01, W10, W11, W12)])
-    ia, ib = _TABLE_INDEX[key]
     return _gather_table(ia, flat), _gather_table(ib, flat)
 
 
@@ -865,6 +861,22 @@ def _fragment(col_weights, NB, KS=4, k0=0, half=False):
 _TABLE_INDEX = {}          # (kind, C, device) -> int64 gather index (-1 = zero) into the flat parameter vector
 
 
+def _table_index(key, make):
+    """the weight-independent gather index (or tuple of indices) under `key`, uploaded on first use.  Published complete: the upload is
+    a copy from pageable host memory, which returns only when the data is on the device, and the uploading stream is synchronised before
+    the entry is stored (once per kind, C and device for the life of the process) — whichever stream or thread finds the entry may read it."""
+    hit = _TABLE_INDEX.get(key)
+    if hit is None:
+        made = make()
+        dev = key[-1]
+        up = lambda a: None if a is None else torch.from_numpy(a).to(dev)
+        hit = tuple(up(a) for a in made) if isinstance(made, tuple) else up(made)
+        if torch.device(dev).type == 'cuda':
+            torch.cuda.current_stream(dev).synchronize()
+        _TABLE_INDEX[key] = hit
+    return hit
+
+
 def _gather_table(index, flat):
     return torch.where(index >= 0, flat[index.clamp(min=0)], torch.zeros((), dtype=flat.dtype, device=flat.device)).contiguous()
 
@@ -893,10 +905,7 @@ def child_cls_table(W):
     ds_read_b128 per lane fetches the weights through which ITS child sees a cell, or zeros).  Built by one device gather through a
     cached index."""
     C = W.shape[1]
-    key = ('cls', C, W.device)
-    if key not in _TABLE_INDEX:
-        _TABLE_INDEX[key] = torch.from_numpy(_cls_index(C)).to(W.device)
-    return _gather_table(_TABLE_INDEX[key], W.detach().reshape(-1))
+    return _gather_table(_table_index(('cls', C, W.device), lambda: _cls_index(C)), W.detach().reshape(-1))
 
 
 def _q4_cls_index(C):
@@ -923,10 +932,7 @@ def _q4_cls_index(C):
 def child_q4_cls_table(W):
     """Table of pcgc_cls_child_q4 (k3 conv 16 -> 1 on a children level, quad-block form)."""
     C = W.shape[1]
-    key = ('q4cls', C, W.device)
-    if key not in _TABLE_INDEX:
-        _TABLE_INDEX[key] = torch.from_numpy(_q4_cls_index(C)).to(W.device)
-    return _gather_table(_TABLE_INDEX[key], W.detach().reshape(-1))
+    return _gather_table(_table_index(('q4cls', C, W.device), lambda: _q4_cls_index(C)), W.detach().reshape(-1))
 
 
 def cls_child_q4(parent_nbr, x, table, bias):
@@ -1049,12 +1055,8 @@ def child_irn_tables(params):
     through cached indices: cheap enough to redo whenever a checkpoint is loaded (R-D sweeps load one per rate)."""
     W00, b00, W01, b01, W10, b10, W11, b11, W12, b12 = params
     C = W00.shape[1]
-    key = ('irn', C, W00.device)
-    if key not in _TABLE_INDEX:
-        ia, ib = _irn_index(C)
-        _TABLE_INDEX[key] = (torch.from_numpy(ia).to(W00.device), None if ib is None else torch.from_numpy(ib).to(W00.device))
+    ia, ib = _table_index(('irn', C, W00.device), lambda: _irn_index(C))
     flat = torch.cat([w.detach().reshape(-1) for w in (W00, W01, W10, W11, W12)])
-    ia, ib = _TABLE_INDEX[key]
     return _gather_table(ia, flat), (None if ib is None else _gather_table(ib, flat))
 
 

@@ -21,6 +21,13 @@ class PCCModel(torch.nn.Module):
         self.entropy_bottleneck.invalidate()
         return super().load_state_dict(conventions.permute_state_dict(state_dict), strict=strict, **kw)
 
+    def weights_changed(self):
+        """The cache contract's explicit call (pcgcv2_amd/derived.py): the kernels read re-laid-out copies of the weights, rebuilt when a
+        parameter's (data_ptr, _version) changes.  Writes through `.data` (`p.data.mul_(s)`, `p.data.copy_(w)`) change neither — call
+        this after them, before the next forward / encode / decode.  Also available on every conv, block and the bottleneck."""
+        from . import derived
+        derived.weights_changed(self)
+
     @torch.no_grad()
     def get_likelihood(self, data, quantize_mode, generator=None):
         """pcc_model.py:15-24 -> (the quantised latent on data's coordinate level, likelihood [N, 8])."""

@@ -110,7 +110,7 @@ class Trainer():
         if optimizer is not None:
             optimizer.zero_grad()
             total.backward()
-            optimizer.step()                                     # (in-place updates bump the parameters' versions: derived tables rebuild)
+            optimizer.step()                                     # (derived.py: the step advances the stamp of every derived table — they rebuild)
         bces = [float(b) for b in bces]
         return {'bce': sum(bces), 'bces': bces, 'bpp': float(bpp), 'sum_loss': float(total), 'out_set': out_set}
 
