@@ -347,6 +347,17 @@ int pcgc_neg_log2_sum(const float* x, int ld, int64_t n, int C, double* bits /*[
 int pcgc_bce_logits(const float* logits, int64_t ld, int64_t n, const uint8_t* truth /*[dev n]*/, const uint8_t* pred /*[dev n] or NULL*/,
                     double* bce, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- lossless mode (lossless.py; csrc/occupancy.hip): what the host coder of the occupancy stream `_O.bin` reads, from a level's logits.
+ *      packed[i] = ctx << 1 | bit with ctx = clamp(rint(16 z_i), -176, 176) + 176 (ties to even, +-inf clamp, NaN -> 176) and bit = truth[i] != 0;
+ *      sums [dev 2] = occupied rows, sum of COST[ctx][bit] in units of 2^-16 bit (integers; per-block partials in `workspace`, added by one
+ *      block; the grid is a function of n alone).  truth = sums = NULL (the decoder's side): contexts only, bit 0, no workspace.
+ *      logits [dev n] with row stride ld; workspace: pcgc_occ_workspace_bytes(n) bytes, 8-byte aligned. ---- */
+size_t pcgc_occ_workspace_bytes(int64_t n);
+int pcgc_occ_symbols(const float* logits, int64_t ld, int64_t n, const uint8_t* truth /*[dev n] or NULL*/, uint16_t* packed /*[dev n]*/,
+                     int64_t* sums /*[dev 2] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
+/* the library's copy of the format tables: P1 uint16 [353], COST int32 [353][2] (either may be NULL) -> number of contexts.  HOST. */
+int pcgc_occ_tables(uint16_t* p1, int32_t* cost);
+
 /* ---- backward pass of the training graph (trainer.py:127-134 `sum_loss.backward()`; csrc/grad.hip).  None of this is on the encode/decode
  *      path.  No floating-point atomics: every reduction has a fixed order (per-workgroup partials in `workspace`, added in ascending
  *      workgroup order by a second stage) and every grid is a function of the shapes alone, so gradients are bitwise reproducible.
@@ -400,6 +411,14 @@ int64_t pcgc_rc_encode_indexed(const uint16_t* cdf, int C, int Lp, const int16_t
                                uint32_t* ckpt /*[host n_ckpt][PCGC_RC_CKPT_WORDS]; unused entries have first symbol 0xFFFFFFFF*/);
 int pcgc_rc_decode_indexed(const uint16_t* cdf, int C, int Lp, const uint8_t* in, int64_t nbytes, int16_t* sym, int64_t n, int n_ckpt,
                            const uint32_t* ckpt);
+/* The same coder with the CDF row chosen per symbol: row ctx[i] of cdf [host R, Lp] instead of row i % C (the occupancy stream of the
+ * lossless mode).  With ctx[i] = i % R the bytes are pcgc_rc_encode's.  encode: bytes, -needed if cap is too small, INT64_MIN for a
+ * symbol or context outside the table.  decode: 0; -2 bad arguments; -3 when `in` is not exactly the stream the encoder writes for the
+ * symbols it decodes to — a cut, extended or damaged stream (the decoded symbols are coded again and compared).  Never reads past nbytes. */
+int64_t pcgc_rc_encode_ctx(const uint16_t* cdf /*[host R,Lp]*/, int R, int Lp, const uint16_t* ctx /*[host n]*/, const int16_t* sym /*[host n]*/,
+                           int64_t n, uint8_t* out /*[host cap]*/, int64_t cap);
+int pcgc_rc_decode_ctx(const uint16_t* cdf, int R, int Lp, const uint16_t* ctx /*[host n]*/, const uint8_t* in, int64_t nbytes,
+                       int16_t* sym /*[host n]*/, int64_t n);
 int pcgc_set_rc_threads(int threads);
 /* The lane-parallel form of the indexed decoder: eight segments per 512-bit register on the calling thread (AVX-512 F/BW/DQ/CD/VL) instead
  * of one or two segments per pool thread.  -1 (default): when the thread budget (pcgc_set_rc_threads) is one or two; 0 never; 1 always.

@@ -88,6 +88,9 @@ SIGNATURES = {
     'pcgc_eb_likelihood': (ci, [vp, ci, i64, ci, vp, f32, vp, vp, vp, sz, vp]),
     'pcgc_neg_log2_sum': (ci, [vp, ci, i64, ci, vp, vp, sz, vp]),
     'pcgc_bce_logits': (ci, [vp, i64, i64, vp, vp, vp, vp, vp, sz, vp]),
+    'pcgc_occ_workspace_bytes': (sz, [i64]),
+    'pcgc_occ_symbols': (ci, [vp, i64, i64, vp, vp, vp, vp, sz, vp]),
+    'pcgc_occ_tables': (ci, [vp, vp]),
     'pcgc_conv_wgrad_workspace_bytes': (sz, [ci, i64, ci, ci]),
     'pcgc_conv_wgrad_rows_per_group': (i64, [ci, i64, ci, ci]),
     'pcgc_conv_wgrad': (ci, [vp, ci, i64, vp, i64, ci, ci, vp, ci, ci, vp, vp, vp, sz, vp]),
@@ -128,6 +131,8 @@ SIGNATURES = {
     'pcgc_set_rc_impl': (ci, [ci]),
     'pcgc_rc_encode_indexed': (i64, [vp, ci, ci, vp, i64, vp, i64, ci, vp]),
     'pcgc_rc_decode_indexed': (ci, [vp, ci, ci, vp, i64, vp, i64, ci, vp]),
+    'pcgc_rc_encode_ctx': (i64, [vp, ci, ci, vp, vp, i64, vp, i64]),
+    'pcgc_rc_decode_ctx': (ci, [vp, ci, ci, vp, vp, i64, vp, i64]),
     'pcgc_set_rc_threads': (ci, [ci]),
     'pcgc_set_rc_lanes': (ci, [ci]),
     'pcgc_set_oct_tiled': (ci, [ci]),

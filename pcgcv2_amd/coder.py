@@ -627,6 +627,9 @@ def _parse_cli(argv):
     p.add_argument("--recolour", action='store_true',
                    help="carry the colours (red green blue) of --filedir onto the decoded cloud: _dec.ply is written with them and the colour "
                         "PSNR of the geometry loss is printed")
+    p.add_argument("--lossless", action='store_true',
+                   help="also write _O.bin, the occupancy stream of the lossless mode (lossless.py): encode, decode, check that the decoded "
+                        "voxel set is the input's, print the bpp of each file")
     return p.parse_args(argv)
 
 
@@ -661,6 +664,10 @@ def _recolour(filedir, x_dec):
 
 def main(argv=None):
     args = _parse_cli(argv)
+    if args.lossless:
+        from . import lossless
+        lossless.run(args.ckptdir, args.filedir, args.outdir)
+        return
     with _Stopwatch('Loading Time', 4, sync=False):
         x = load_sparse_tensor(args.filedir, device)
     os.makedirs(args.outdir, exist_ok=True)

@@ -642,6 +642,87 @@ extern "C" int pcgc_rc_decode_indexed(const uint16_t* cdf, int C, int Lp, const 
     return rc_decode_starts(cdf, C, Lp, in, nbytes, sym, n, starts, rc_threads());
 }
 
+// ---- the same coder with the CDF row chosen per symbol (the occupancy stream `_O.bin` of the lossless mode, lossless.py): row ctx[i]
+// instead of row i % C, and nothing else different — the step below is rc_encode_body's, formula for formula, so with ctx[i] = i % R the
+// bytes are pcgc_rc_encode's.  Portable scalar code on both sides.
+extern "C" int64_t pcgc_rc_encode_ctx(const uint16_t* cdf, int R, int Lp, const uint16_t* ctx, const int16_t* sym, int64_t n, uint8_t* out, int64_t cap) {
+    if (!cdf || R < 1 || Lp < 2 || n < 0 || cap < 0 || (n > 0 && (!ctx || !sym)) || (cap > 0 && !out)) return INT64_MIN;
+    const int top_symbol = Lp - 2;
+    {
+        unsigned bad = 0;
+        for (int64_t i = 0; i < n; ++i) bad |= (unsigned)((unsigned)sym[i] > (unsigned)top_symbol) | (unsigned)((int)ctx[i] >= R);
+        if (bad) return INT64_MIN;
+    }
+    const std::vector<uint32_t> rows = widen_rows(cdf, R, Lp);
+    Sink sink{out, cap};
+    uint32_t low = 0; uint64_t span = 1ull << 32; uint64_t pending = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const uint32_t* row = rows.data() + (size_t)ctx[i] * Lp; const int s = sym[i];
+        const uint32_t c_lo = (uint32_t)((span * row[s]) >> 16), c_hi = (uint32_t)((span * row[s + 1]) >> 16);
+        const uint32_t lo = low + c_lo, hi = low + c_hi - 1;
+        const int nshare = clz32(lo ^ hi);
+        const int t = clz32((((~lo | hi) << 1) | 1u) & (0xFFFFFFFFu >> nshare));
+        low = (uint32_t)((uint64_t)lo << t) & 0x7FFFFFFFu;
+        span = (uint64_t)(c_hi - c_lo) << t;
+        if (nshare) {                                      // first shared bit, `pending` copies of its complement, the other shared bits
+            const uint32_t bits = (uint32_t)(((uint64_t)lo << nshare) >> 32), first = bits >> (nshare - 1);
+            sink.put(first, 1); sink.put_run(first ^ 1u, pending);
+            sink.put(bits & ((1u << (nshare - 1)) - 1u), nshare - 1);
+            pending = 0;
+        }
+        pending += (uint64_t)(t - nshare);
+    }
+    ++pending;
+    const uint32_t last = low < 0x40000000u ? 0u : 1u;
+    sink.put(last, 1); sink.put_run(last ^ 1u, pending); sink.flush();
+    if (sink.len > cap) return -sink.len;
+    return sink.len;
+}
+// Decodes n symbols and then REQUIRES the stream to be the one the encoder writes for them: the decoded symbols are coded again and
+// compared with the input, length and bytes.  The range decoder itself cannot tell a damaged stream from a sound one (past the end it
+// reads zeros; any 32-bit window names some symbol), and a stream cut behind its last non-zero byte even decodes to the right symbols.
+// The termination of the coder makes the test exact: every continuation of a sound stream's bits decodes to the same symbols, so no
+// proper prefix and no extension of a sound stream is itself a sound stream for the same contexts.
+// Returns 0, -2 on bad arguments, -3 when the stream is not the coded form of what it decodes to (short, over-long or damaged).
+// Reads `in` up to nbytes only (it works on a zero-padded copy).
+extern "C" int pcgc_rc_decode_ctx(const uint16_t* cdf, int R, int Lp, const uint16_t* ctx, const uint8_t* in, int64_t nbytes, int16_t* sym, int64_t n) {
+    if (!cdf || R < 1 || Lp < 2 || n < 0 || nbytes < 0 || (n > 0 && (!ctx || !sym)) || (nbytes > 0 && !in)) { pcgc_set_error("rc_decode_ctx: bad arguments"); return -2; }
+    for (int64_t i = 0; i < n; ++i) if ((int)ctx[i] >= R) { pcgc_set_error("rc_decode_ctx: context %d of symbol %lld outside the %d rows", (int)ctx[i], (long long)i, R); return -2; }
+    std::vector<uint8_t> padded((size_t)nbytes + 64, 0);
+    if (nbytes) std::memcpy(padded.data(), in, (size_t)nbytes);
+    if (n > 0) {
+        const std::vector<uint32_t> rows = widen_rows(cdf, R, Lp);
+        Source src{padded.data(), nbytes + 8, 4};
+        uint32_t low = 0, high = 0xFFFFFFFFu;
+        uint32_t value = ((uint32_t)padded[0] << 24) | ((uint32_t)padded[1] << 16) | ((uint32_t)padded[2] << 8) | padded[3];
+        for (int64_t i = 0; i < n; ++i) {                    // (rc_decode_scalar_seg with the row taken from ctx[i])
+            const uint32_t* row = rows.data() + (size_t)ctx[i] * Lp;
+            const uint64_t span = (uint64_t)high - (uint64_t)low + 1;
+            const uint32_t target = (uint16_t)((((uint64_t)value - (uint64_t)low + 1) * 0x10000ull - 1) / span);
+            int s = 0;
+            while (row[s + 1] <= target) ++s;              // row[top + 1] = 0x10000 > target: no bound check needed
+            sym[i] = (int16_t)s;
+            if (i == n - 1) break;
+            high = (low - 1) + (uint32_t)((span * row[s + 1]) >> 16);
+            low = low + (uint32_t)((span * row[s]) >> 16);
+            const int nshare = clz32(low ^ high);
+            if (nshare) { low <<= nshare; high = (high << nshare) | ((1u << nshare) - 1u); value = (value << nshare) | src.take(nshare); }
+            while (low >= 0x40000000u && high < 0xC0000000u) {
+                int m = clz32(~(low << 1)); const int mz = clz32(high << 1); if (mz < m) m = mz; if (m > 31) m = 31;
+                low = (low << m) & 0x7FFFFFFFu; high = (high << m) | 0x80000000u | ((1u << m) - 1u);
+                value = ((value << m) | src.take(m)) ^ 0x80000000u;
+            }
+        }
+    }
+    std::vector<uint8_t> again((size_t)nbytes + 8);
+    const int64_t len = pcgc_rc_encode_ctx(cdf, R, Lp, ctx, sym, n, again.data(), nbytes);
+    if (len != nbytes || (nbytes && std::memcmp(again.data(), in, (size_t)nbytes) != 0)) {
+        pcgc_set_error("rc_decode_ctx: the stream (%lld bytes) is not the coded form of the %lld symbols it decodes to (cut, extended or damaged)", (long long)nbytes, (long long)n);
+        return -3;
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------ octree codec
 // Breadth-first occupancy octree over the Morton-sorted points; each node's 8-bit child occupancy is coded as 8 binary
 // decisions with an adaptive binary range coder (12-bit probabilities, carry-propagating 32-bit range, LZMA-style);

@@ -1,0 +1,275 @@
+"""Lossless mode: the lossy codec's four files plus `_O.bin`, the true occupancy of every candidate voxel of the three decoder levels,
+range-coded under the probability the decoder's own logit gives it (occupancy_model.py).  A lossy decoder still decodes the four files;
+a lossless one reads `_O.bin` as well, prunes by the coded bits instead of by top-k, and returns the input's voxel set exactly.
+
+Why it works: the decoder's kernels are bit-for-bit reproducible (no floating-point atomics, one fmaf chain per output row whatever kernel
+family runs it), so an encoder that runs the decoder network on the latent AS THE DECODER RECONSTRUCTS IT — from the int16 symbols and
+min_v, on the sorted stride-8 level — and prunes every level by the truth sees the very logits the decoder will see.  Both sides go through
+the same two functions below (`_latent_level`, `_logits`).
+
+`_O.bin`, little endian:
+    4s  magic "PCGL" | u32 version (1) | u32 CRC-32 of the format tables (occupancy_model.table_crc)
+    3 x (u64 candidate rows, u64 payload bytes)          levels at stride 4, 2, 1; rows of level l + 1 = 8 x occupied rows of level l
+    3 payloads                                           ops.rc_encode_ctx of the level's bits (0 empty, 1 occupied) in candidate-row
+                                                         order, symbol i under CDF row ctx[i]
+Level l + 1's contexts need level l decoded, so the payloads are separate streams.
+
+    python -m pcgcv2_amd.lossless --ckptdir CKPT --filedir CLOUD.ply [--outdir DIR]
+"""
+import os
+import struct
+import time
+
+import numpy as np
+import torch
+
+from . import occupancy_model, ops
+from ._lib import PcgcError
+from .coder import Coder, _dump, _slurp, stream_bits, STREAMS
+from .data_utils import isin_mask
+from .sparse import CoordMap, SparseTensor, require_gpu
+
+SUFFIX = '_O.bin'
+MAGIC, VERSION = b'PCGL', 1
+_HEAD = struct.Struct('<4sII')
+_LEVELS = struct.Struct('<6Q')                    # (rows, bytes) of the three levels
+LEVELS = 3
+
+
+class LosslessCoder():
+    """Coder(model, filename) plus the occupancy stream.  One frame per call."""
+
+    def __init__(self, model, filename):
+        self.model = model
+        self.filename = filename
+        self.coder = Coder(model, filename)
+        self._cdf = occupancy_model.cdf_rows()
+        self.times = None                         # measurement hook (tools/lossless_time.py): a dict -> seconds per phase, with synchronisation
+
+    # ---- measurement hook ---------------------------------------------------------------------------------------------------------------
+    def _tick(self, phase, t0, dev=None):
+        if self.times is None:
+            return 0.0
+        if dev is not None:
+            torch.cuda.synchronize(dev)
+        now = time.perf_counter()
+        if phase is not None:
+            self.times[phase] = self.times.get(phase, 0.0) + now - t0
+        return now
+
+    # ---- what both sides run ------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _latent_level(sym_d, min_v, coords8):
+        """the latent as a decoder holds it: features from the int16 symbols and min_v, on the sorted stride-8 level"""
+        lvl8 = coords8 if isinstance(coords8, CoordMap) else CoordMap(coords8, 8, unique=True)
+        if len(lvl8) != sym_d.shape[0]:
+            raise PcgcError(f'{len(lvl8)} stride-8 coordinates but {sym_d.shape[0]} latent rows')
+        if len(lvl8) and lvl8._prepared_up is None:
+            lvl8.prepare_up()
+        return SparseTensor(features=ops.desymbolize(sym_d, min_v), coordinate_map=lvl8)
+
+    def _logits(self, out, l):
+        """decoder level l up to its classification head -> (candidates with their features, logits [8 n, 1])"""
+        dec = self.model.decoder
+        out = getattr(dec, f'up{l}')(out, relu=True)
+        out = getattr(dec, f'conv{l}')(out, relu=True)
+        out = getattr(dec, f'block{l}')(out)
+        return out, getattr(dec, f'conv{l}_cls')(out).F
+
+    # ---- encoder ------------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _single_frame(x):
+        if not isinstance(x, SparseTensor):
+            raise TypeError('LosslessCoder codes a SparseTensor')
+        if len(x) == 0:
+            raise ValueError('LosslessCoder: an empty cloud')
+        if len(x.cmap.batch_rows) != 1:
+            raise ValueError(f'LosslessCoder codes one frame at a time; got a batch of {len(x.cmap.batch_rows)} items')
+
+    def _truth_levels(self, x):
+        """the encoder pyramid's levels at stride 4, 2, 1 (of the cloud as Coder.encode ingests it: the sets are the input's)"""
+        xi = self.coder._ingest(x)
+        xi.cmap.build_pyramid(3)
+        l2 = xi.cmap.down()[0]
+        return xi, [l2.down()[0], l2, xi.cmap]
+
+    def _enhance(self, x, y, code):
+        """run the decoder network on the latent y (sorted, as Coder.encode returns it) under teacher forcing by the truth alone
+        -> (record, payloads or None)"""
+        dev = x.device
+        t = self._tick(None, 0.0, dev)
+        _, truths = self._truth_levels(x)
+        min_v, _, sym_h = ops.quantize_symbols(y.F)
+        out = self._latent_level(torch.from_numpy(sym_h).to(dev), min_v, y.C)
+        t = self._tick('copies', t, dev)
+        rows, units, payloads = [], 0, []
+        for l in range(LEVELS):
+            out, logits = self._logits(out, l)
+            truth = isin_mask(out.cmap.C, truths[l])
+            t = self._tick('network', t, dev)
+            packed, sums = ops.occ_symbols(logits, truth)
+            t = self._tick('k_occ_symbols', t, dev)
+            words, occupied, cost = ops.occ_words_host(packed, sums)
+            t = self._tick('copies', t, dev)
+            if occupied != len(truths[l]):
+                raise PcgcError(f'lossless encode: level {l} holds {len(truths[l])} voxels but {occupied} of its {len(words)} candidates are '
+                                'among them: the input is not a set of distinct voxels of one frame')
+            rows.append(len(words))
+            units += cost
+            if code:
+                payloads.append(ops.rc_encode_ctx(self._cdf, words >> 1, words & 1))
+                t = self._tick('host coder', t)
+            out = self.model.decoder.pruning(out, truth, n_keep=occupied)
+            t = self._tick('network', t, dev)
+        return {'est_units_O': units, 'est_bits_O': units / occupancy_model.COST_UNIT, 'rows': rows}, payloads
+
+    @torch.no_grad()
+    def encode(self, x, postfix=''):
+        """Coder.encode(x, postfix) unchanged, then `_O.bin` -> {bits_O, est_bits_O, rows (candidates per level), ...}"""
+        self._single_frame(x)
+        with torch.cuda.device(x.device):
+            t = self._tick(None, 0.0, x.device)
+            y = self.coder.encode(x, postfix)
+            self._tick('lossy encode', t, x.device)
+            record, payloads = self._enhance(x, y, code=True)
+            t = self._tick(None, 0.0)
+            sizes = [v for r, p in zip(record['rows'], payloads) for v in (r, len(p))]
+            blob = _HEAD.pack(MAGIC, VERSION, occupancy_model.table_crc()) + _LEVELS.pack(*sizes) + b''.join(payloads)
+            _dump(self.filename + postfix + SUFFIX, blob)
+            self._tick('host coder', t)
+        record['bits_O'] = 8 * len(blob)
+        record['payload_bytes'] = [len(p) for p in payloads]
+        return record
+
+    @torch.no_grad()
+    def estimate(self, x):
+        """est_bits_O of encode(x) — the ideal length of the occupancy stream in bits — without writing anything"""
+        self._single_frame(x)
+        with torch.cuda.device(x.device):
+            xi, _ = self._truth_levels(x)
+            lvl8 = xi.cmap.build_pyramid(3)
+            y_list = self.model.encoder(xi)
+            order = ops.sort_zyx(lvl8.C)                                     # (the order Coder.encode codes the latent in)
+            y = SparseTensor(ops.gather_feats(y_list[0].F, order), coordinate_map=CoordMap(ops.gather_coords(lvl8.C, order), lvl8.stride, unique=True))
+            return self._enhance(x, y, code=False)[0]['est_bits_O']
+
+    # ---- decoder ------------------------------------------------------------------------------------------------------------------------
+    def _read_stream(self, postfix):
+        path = self.filename + postfix + SUFFIX
+        blob = _slurp(path)
+        if len(blob) < _HEAD.size + _LEVELS.size:
+            raise PcgcError(f'{path}: {len(blob)} bytes, shorter than its header')
+        magic, version, crc = _HEAD.unpack_from(blob, 0)
+        if magic != MAGIC:
+            raise PcgcError(f'{path}: not an occupancy stream (magic {magic!r})')
+        if version != VERSION:
+            raise PcgcError(f'{path}: version {version}; this decoder reads version {VERSION}')
+        if crc != occupancy_model.table_crc():
+            raise PcgcError(f'{path}: coded with other probability tables (CRC-32 {crc:08x}, here {occupancy_model.table_crc():08x})')
+        sizes = _LEVELS.unpack_from(blob, _HEAD.size)
+        rows, nbytes = sizes[0::2], sizes[1::2]
+        if len(blob) != _HEAD.size + _LEVELS.size + sum(nbytes):
+            raise PcgcError(f'{path}: {len(blob)} bytes, but the header declares payloads of {list(nbytes)} bytes')
+        offs = np.cumsum([_HEAD.size + _LEVELS.size] + list(nbytes))
+        return rows, [blob[offs[l]:offs[l + 1]] for l in range(LEVELS)]
+
+    @torch.no_grad()
+    def decode(self, postfix=''):
+        """reads `_C.bin`, `_F.bin`, `_H.bin` and `_O.bin` -> the stride-1 sparse tensor whose coordinate set is the input's.  Raises
+        PcgcError on a stream that is damaged, cut, extended or inconsistent; never returns a cloud from one."""
+        dev = require_gpu(next(self.model.decoder.parameters()).device)
+        with torch.cuda.device(dev):
+            return self._decode(postfix, dev)
+
+    def _decode(self, postfix, dev):
+        t = self._tick(None, 0.0, dev)
+        rows, payloads = self._read_stream(postfix)
+        fc = self.coder.feature_coder
+        sym_h, min_v = fc.decode_symbols(postfix=postfix, device=dev)
+        lvl8 = self.coder._decode_geometry(postfix, dev, torch.cuda.current_stream(dev))
+        t = self._tick('host coder', t, dev)
+        out = self._latent_level(torch.from_numpy(np.ascontiguousarray(sym_h)).to(dev), min_v, lvl8)
+        t = self._tick('copies', t, dev)
+        parents = len(out)
+        for l in range(LEVELS):
+            if rows[l] != 8 * parents:
+                raise PcgcError(f'{self.filename + postfix + SUFFIX}: level {l} declares {rows[l]} candidate rows; the level above has '
+                                f'{parents} voxels, i.e. {8 * parents} candidates')
+            out, logits = self._logits(out, l)
+            t = self._tick('network', t, dev)
+            packed, _ = ops.occ_symbols(logits)
+            t = self._tick('k_occ_symbols', t, dev)
+            words, _, _ = ops.occ_words_host(packed, None)
+            t = self._tick('copies', t, dev)
+            bits = ops.rc_decode_ctx(self._cdf, words >> 1, payloads[l])
+            t = self._tick('host coder', t)
+            parents = int(bits.sum())
+            if parents == 0:
+                raise PcgcError(f'{self.filename + postfix + SUFFIX}: level {l} decodes to no voxel at all')
+            mask = torch.from_numpy(bits.astype(np.uint8)).to(dev)
+            t = self._tick('copies', t, dev)
+            out = self.model.decoder.pruning(out, mask, n_keep=parents)
+            t = self._tick('network', t, dev)
+        return out
+
+
+def occupancy_bits(prefix, postfix=''):
+    """bits of `_O.bin` of one coded cloud"""
+    return os.path.getsize(prefix + postfix + SUFFIX) * 8
+
+
+def same_voxels(a, b):
+    """True iff two [n, 4] coordinate tensors hold the same set of rows"""
+    if a.shape != b.shape:
+        return False
+    a, b = a.contiguous(), b.contiguous()
+    return bool(torch.equal(ops.gather_coords(a, ops.sort_zyx(a)), ops.gather_coords(b, ops.sort_zyx(b))))
+
+
+# ------------------------------------------------------------------------------------------------ CLI
+def run(ckptdir, filedir, outdir):
+    """encode, decode, check set equality, print the bpp of each file and the total"""
+    from .coder import device, _Stopwatch
+    from .data_utils import load_sparse_tensor, write_ply_ascii_geo
+    from .pcc_model import PCCModel
+    x = load_sparse_tensor(filedir, device)
+    os.makedirs(outdir, exist_ok=True)
+    prefix = os.path.join(outdir, os.path.split(filedir)[-1].split('.')[0])
+    print(prefix)
+    if not os.path.exists(ckptdir):
+        raise FileNotFoundError(ckptdir)
+    model = PCCModel().to(device)
+    model.load_state_dict(torch.load(ckptdir, map_location=device)['model'])
+    print('load checkpoint from \t', ckptdir)
+    coder = LosslessCoder(model=model, filename=prefix)
+    with _Stopwatch('Enc Time'):
+        record = coder.encode(x)
+    with _Stopwatch('Dec Time'):
+        x_dec = coder.decode()
+    exact = same_voxels(x.C, x_dec.C)
+    names = STREAMS + (SUFFIX,)
+    bits = np.append(stream_bits(prefix), occupancy_bits(prefix))
+    bpps = (bits / len(x)).round(3)
+    for name, b, bpp in zip(names, bits, bpps):
+        print(f'{name}:\t {b} bits\t {bpp} bpp')
+    print('bits:\t', sum(bits), '\nbpps:\t', sum(bpps).round(3))
+    print('ideal bits of _O.bin:\t', round(record['est_bits_O'], 1), '\ncandidate rows:\t', record['rows'])
+    print('lossless:\t', 'exact' if exact else 'MISMATCH')
+    write_ply_ascii_geo(prefix + '_dec.ply', x_dec.C.detach().cpu().numpy()[:, 1:])
+    if not exact:
+        raise PcgcError(f'{prefix}: the decoded voxel set differs from the input ({len(x_dec)} against {len(x)} voxels)')
+    return record
+
+
+def main(argv=None):
+    import argparse
+    p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument("--ckptdir", default='ckpts/r3_0.10bpp.pth')
+    p.add_argument("--filedir", default='../../../testdata/8iVFB/longdress_vox10_1300.ply')
+    p.add_argument("--outdir", default='./output')
+    args = p.parse_args(argv)
+    run(args.ckptdir, args.filedir, args.outdir)
+
+
+if __name__ == '__main__':
+    main()

@@ -1529,6 +1529,46 @@ def bce_logits(logits, truth, pred=None):
     return bce, counts
 
 
+# ------------------------------------------------------------------------------------------------ lossless mode (csrc/occupancy.hip)
+def occ_symbols(logits, truth=None):
+    """One pass over a level's logits ([n] or [n, 1] fp32 view) -> packed int16 [n] = ctx << 1 | bit (occupancy_model.py: ctx from the
+    logit, bit = truth[i] != 0; the words are < 2^10), and, with the uint8 truth mask, sums int64 [2] = (occupied rows, ideal code
+    length in 2^-16 bit).  truth=None (the decoder's side): contexts only, (packed, None).  Both are views of ONE buffer, sums first."""
+    _f32(logits, 'logits')
+    n, dev = logits.shape[0], logits.device
+    if logits.dim() > 2 or (logits.dim() == 2 and logits.shape[1] != 1):
+        raise PcgcError(f'occ_symbols: logits {tuple(logits.shape)}, expected [n] or [n, 1]')
+    ld = max(int(logits.stride(0)), 1)
+    buf = torch.empty(8 + n, dtype=torch.int16, device=dev)                    # [sums as 2 int64 = 8 int16 | packed]
+    packed, sums, ws, ws_bytes = buf[8:], None, None, 0
+    if truth is not None:
+        if _dev(truth, torch.uint8, 'truth').shape[0] != n:
+            raise PcgcError(f'occ_symbols: {n} logits against a mask of {truth.shape[0]} rows')
+        sums = buf[:8].view(torch.int64)
+        ws_bytes = int(lib().pcgc_occ_workspace_bytes(n))
+        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    check(lib().pcgc_occ_symbols(_p(logits), ld, n, _p(truth), _p(packed), _p(sums), _p(ws), ws_bytes, _stream(logits)), 'occ_symbols')
+    return packed, sums
+
+
+def occ_words_host(packed, sums=None):
+    """what occ_symbols returned, brought to the host in ONE synchronising copy -> (words uint16 ndarray [n] in candidate-row order,
+    occupied rows, ideal code length in 2^-16 bit); the two numbers are None without sums."""
+    if sums is None:
+        return packed.cpu().numpy().view(np.uint16), None, None
+    host = packed._base.cpu().numpy()                                          # [sums | packed]: one buffer (occ_symbols)
+    both = host[:8].view(np.int64)
+    return host[8:].view(np.uint16), int(both[0]), int(both[1])
+
+
+def occ_tables():
+    """the library's copy of the lossless mode's format tables -> (P1 uint16 [353], COST int32 [353, 2]) (host call)"""
+    n = int(lib().pcgc_occ_tables(None, None))
+    p1, cost = np.empty(n, np.uint16), np.empty((n, 2), np.int32)
+    lib().pcgc_occ_tables(p1.ctypes.data, cost.ctypes.data)
+    return p1, cost
+
+
 # ------------------------------------------------------------------------------------------------ backward pass (csrc/grad.hip)
 def conv_wgrad_rows_per_group(K, n_rows, Cin, Cout):
     """consecutive rows one workgroup of conv_wgrad reduces (a function of the shapes alone)"""
@@ -2125,6 +2165,37 @@ def rc_decode(cdf_u16, data, n, index=None):
         idx = np.ascontiguousarray(index, dtype=np.uint32).reshape(-1, RC_CKPT_WORDS)
         check(lib().pcgc_rc_decode_indexed(cdf.ctypes.data, C, Lp, src.ctypes.data, src.size, out.ctypes.data, n, idx.shape[0],
                                            idx.ctypes.data), 'rc_decode_indexed')
+    return out
+
+
+def rc_encode_ctx(cdf_u16, ctx, sym):
+    """range-coded bytes of sym [n] with symbol i coded under row ctx[i] of cdf_u16 [R, Lp] (rc_encode's coder, the row chosen per symbol)"""
+    cdf = _np(cdf_u16, np.uint16)
+    ctx, sym = _np(ctx, np.uint16).ravel(), _np(sym, np.int16).ravel()
+    if ctx.size != sym.size:
+        raise PcgcError(f'rc_encode_ctx: {sym.size} symbols but {ctx.size} contexts')
+    R, Lp = cdf.shape
+    cap = sym.size // 4 + 64
+    while True:
+        buf = np.empty(cap, np.uint8)
+        n = int(lib().pcgc_rc_encode_ctx(cdf.ctypes.data, R, Lp, ctx.ctypes.data, sym.ctypes.data, sym.size, buf.ctypes.data, cap))
+        if n >= 0:
+            return buf[:n].tobytes()
+        if n == -(2 ** 63):
+            raise PcgcError('rc_encode_ctx: symbol or context outside the CDF table')
+        cap = -n
+
+
+def rc_decode_ctx(cdf_u16, ctx, data):
+    """-> int16 [n], n = len(ctx).  Raises PcgcError unless `data` is exactly the stream rc_encode_ctx writes for the symbols it decodes
+    to: a cut, extended or damaged stream is refused, never returned as symbols."""
+    cdf = _np(cdf_u16, np.uint16)
+    ctx = _np(ctx, np.uint16).ravel()
+    R, Lp = cdf.shape
+    src = np.frombuffer(data, np.uint8)
+    out = np.empty(ctx.size, np.int16)
+    check(lib().pcgc_rc_decode_ctx(cdf.ctypes.data, R, Lp, ctx.ctypes.data, src.ctypes.data if src.size else None, src.size,
+                                   out.ctypes.data, ctx.size), 'rc_decode_ctx')
     return out
 
 

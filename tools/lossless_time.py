@@ -1,0 +1,109 @@
+#!/usr/bin/env python3
+"""Time of one lossless encode and decode (pcgcv2_amd/lossless.py) on the bench frame (shell10, 786 632 points), synthetic weights, warm, in
+this fresh process: the median of --repeat runs end to end, next to one lossy Coder.encode + decode pair in the same process, and — from a
+second set of runs with a device synchronisation between the phases — the split into network, k_occ_symbols, host coder and copies.
+Also: candidate rows per level, bits of `_O.bin` against its ideal length, bpp (synthetic weights: says nothing about trained models), and
+the gap between the ideal length and loss.get_bce on the same forward point.  With --trace it re-runs itself once under
+`rocprofv3 --kernel-trace --stats` (a fresh child process) and prints the k_occ_* rows.
+    tools/lossless_time.py [--cloud NAME] [--repeat K] [--trace]"""
+import argparse, csv, glob, json, os, subprocess, sys, tempfile, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+ap = argparse.ArgumentParser()
+ap.add_argument('--cloud', default='shell10')
+ap.add_argument('--repeat', type=int, default=7)
+ap.add_argument('--trace', action='store_true', help='also one rocprofv3 --kernel-trace --stats run of two encode + decode pairs (child process)')
+ap.add_argument('--one-call', action='store_true', help=argparse.SUPPRESS)
+args = ap.parse_args()
+
+
+def trace_table():
+    with tempfile.TemporaryDirectory() as d:
+        cmd = ['rocprofv3', '--kernel-trace', '--stats', '--output-format', 'csv', '-d', d, '--', sys.executable, os.path.abspath(__file__),
+               '--cloud', args.cloud, '--one-call']
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        if r.returncode != 0:
+            raise SystemExit('rocprofv3 failed:\n' + r.stderr[-2000:])
+        rows = []
+        for path in glob.glob(os.path.join(d, '**', '*kernel_stats.csv'), recursive=True):
+            rows += list(csv.DictReader(open(path)))
+    return [{'kernel': r['Name'][:60], 'calls': int(r['Calls']), 'total_us': round(float(r['TotalDurationNs']) / 1e3, 1),
+             'mean_us': round(float(r['AverageNs']) / 1e3, 1)} for r in rows if 'k_occ_' in r.get('Name', '')]
+
+
+import numpy as np
+import torch
+import pcgcv2_amd
+pcgcv2_amd.configure_host_threads()
+from pcgcv2_amd import lossless, ops, synthetic
+from pcgcv2_amd.coder import Coder, stream_bits
+from pcgcv2_amd.data_utils import isin_mask
+from pcgcv2_amd.pcc_model import PCCModel
+from pcgcv2_amd.sparse import SparseTensor
+
+dev = torch.device('cuda:0')
+model = PCCModel().to(dev)
+model.load_state_dict(synthetic.synthetic_state_dict())
+pts = synthetic.cloud(args.cloud, device=dev)
+coords = torch.cat([torch.zeros((len(pts), 1), dtype=torch.int32, device=dev), pts], 1).contiguous()
+x = SparseTensor(torch.ones((len(pts), 1), device=dev), coordinates=coords, tensor_stride=1, device=dev)
+tmp = tempfile.TemporaryDirectory()
+prefix = os.path.join(tmp.name, 'frame')
+exact, lossy = lossless.LosslessCoder(model, prefix), Coder(model, prefix + '_lossy')
+
+if args.one_call:
+    for _ in range(2):
+        exact.encode(x); exact.decode()
+    torch.cuda.synchronize()
+    raise SystemExit(0)
+
+
+def median_ms(fn, runs):
+    fn(); torch.cuda.synchronize()                                    # (warm: code objects, derived tables, allocator)
+    times = []
+    for _ in range(runs):
+        torch.cuda.synchronize(); t = time.perf_counter(); fn(); torch.cuda.synchronize(); times.append(time.perf_counter() - t)
+    return round(float(np.median(times)) * 1e3, 3)
+
+
+def phases_ms(fn, runs):
+    out = []
+    for _ in range(runs):
+        exact.times = {}
+        fn(); torch.cuda.synchronize()
+        out.append(exact.times)
+    exact.times = None
+    return {k: round(float(np.median([o.get(k, 0.0) for o in out])) * 1e3, 3) for k in out[0]}
+
+
+runs = max(args.repeat, 5)
+record = exact.encode(x)
+out = exact.decode()
+report = {'cloud': args.cloud, 'points': len(pts), 'runs': runs, 'weights': 'synthetic (the rate says nothing about trained models)',
+          'exact': lossless.same_voxels(out.C, x.C), 'candidate_rows': record['rows'],
+          'bits_O': record['bits_O'], 'ideal_bits_O': round(record['est_bits_O'], 1), 'bpp_O': round(record['bits_O'] / len(pts), 4),
+          'bpp_lossy_files': round(float(stream_bits(prefix).sum()) / len(pts), 4)}
+report['median_ms'] = {'lossless_encode': median_ms(lambda: exact.encode(x), runs), 'lossless_decode': median_ms(exact.decode, runs),
+                       'lossy_encode': median_ms(lambda: lossy.encode(x), runs), 'lossy_decode': median_ms(lossy.decode, runs)}
+report['phases_ms_synchronised'] = {'encode': phases_ms(lambda: exact.encode(x), runs), 'decode': phases_ms(exact.decode, runs)}
+
+# the same forward point through loss.get_bce: teacher forcing by the truth alone, BCE of every level's logits in bits
+with torch.no_grad():
+    xi, truths = exact._truth_levels(x)
+    y = exact.coder.encode(x)
+    min_v, _, sym_h = ops.quantize_symbols(y.F)
+    level = exact._latent_level(torch.from_numpy(sym_h).to(dev), min_v, y.C)
+    bce_bits, candidates = 0.0, 0
+    for l in range(lossless.LEVELS):
+        level, logits = exact._logits(level, l)
+        truth = isin_mask(level.cmap.C, truths[l])
+        bce_bits += float(ops.bce_logits(logits, truth)[0].item())
+        candidates += logits.shape[0]
+        level = model.decoder.pruning(level, truth, n_keep=len(truths[l]))
+report['bce_bits_same_point'] = round(bce_bits, 1)
+report['ideal_minus_bce_bits_per_candidate'] = (record['est_bits_O'] - bce_bits) / candidates
+report['first_order_bound_bits_per_candidate'] = (1 / 32) / float(np.log(2.0))
+if args.trace:
+    report['kernel_trace'] = trace_table()
+print(json.dumps(report, indent=1))
