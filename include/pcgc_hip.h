@@ -358,6 +358,37 @@ int pcgc_occ_symbols(const float* logits, int64_t ld, int64_t n, const uint8_t* 
 /* the library's copy of the format tables: P1 uint16 [353], COST int32 [353][2] (either may be NULL) -> number of contexts.  HOST. */
 int pcgc_occ_tables(uint16_t* p1, int32_t* cost);
 
+/* ---- lossless mode, `_O.bin` version 2 (csrc/occupancy_rans.hip): the same bits coded ON THE DEVICE by interleaved rANS.  One wave per
+ *      chunk of 64 S rows; 64 independent states, one per lane, share one stream of 32-bit words.  A level's payload, little endian:
+ *          u32 S             steps per chunk, 1 .. 2^24
+ *          u32 K             chunks = ceil(rows / (64 S))  (rows = 0: K = 0)
+ *          K x 64 x u64      the decoder's initial state of every lane, chunk by chunk, lane 0 .. 63
+ *          K x u32           W_k: 32-bit words of chunk k
+ *          u32 words         chunk 0's W_0 words, then chunk 1's, ...
+ *      Chunk k covers rows [64 S k, min(rows, 64 S (k + 1))); lane j codes rows base + 64 t + j, t = 0 .. S - 1.  64-bit state, L = 2^31,
+ *      probabilities straight from P1: bit b under ctx has f = b ? P1 : 65536 - P1, c = b ? 65536 - P1 : 0.
+ *      Encoder, per chunk: every lane starts at x = L; steps t = S - 1 .. 0, lanes j = 63 .. 0 within a step, rows past the end skipped; at a
+ *      row: if x >= f << 47, emit x & 0xffffffff and x >>= 32; then x = ((x / f) << 16) + x % f + c.  The stream is the emitted words in
+ *      reverse order; the final x of each lane is its stored state (a lane without rows stores L).
+ *      Decoder, per chunk: steps t = 0 .. S - 1, lanes j = 0 .. 63; at a row: s = x & 0xffff, b = s >= 65536 - P1, x = f (x >> 16) + s - c;
+ *      if x < L, x = x << 32 | next word (within a step, words go to the renormalising lanes in ascending lane order).  A chunk is sound
+ *      iff every stored state is in [2^31, 2^63), exactly W_k words were consumed and every lane ends at x == L; a word index at or past
+ *      W_k reads as 0 and marks the chunk unsound.  The decoder reads nothing outside a chunk's words, whatever the bytes say.
+ *      rows < 2^31.  workspace: pcgc_occ_rans_workspace_bytes(n, steps) device bytes, 8-byte aligned (no allocation inside); the decoder
+ *      uses its first 32 + 8 ceil(K / 2) bytes only and accepts as little. ---- */
+size_t pcgc_occ_rans_workspace_bytes(int64_t n, int steps);
+/* packed [dev n] as pcgc_occ_symbols writes it -> payload [dev, 8-byte aligned, capacity >= 8 + 516 K + 4 n bytes] in the layout above;
+ * host3 [host 3] = the payload's length in bytes and, when sums (pcgc_occ_symbols' [dev 2]) is given, sums[0] and sums[1]: ONE small
+ * synchronising copy.  The caller then copies the finished payload. */
+int pcgc_occ_rans_encode(const uint16_t* packed /*[dev n]*/, int64_t n, int steps, const int64_t* sums /*[dev 2] or NULL*/, uint8_t* payload,
+                         size_t payload_capacity, int64_t* host3, void* workspace, size_t workspace_bytes, void* stream);
+/* packed [dev n]: the contexts (bit 0 is ignored: pcgc_occ_symbols with truth = NULL); payload [dev, 8-byte aligned] of payload_bytes bytes
+ * whose head the caller has read: steps = its S, and its K, the table sizes and the sum of W_k agree with n and payload_bytes
+ * (ops.occ_rans_decode checks them on the host; here K follows from n and steps, and no access leaves the payload in any case)
+ * -> mask [dev n] (0 empty, 1 occupied); host2 [host 2] = occupied rows, unsound chunks (0: the payload is sound), in one small copy. */
+int pcgc_occ_rans_decode(const uint16_t* packed /*[dev n]*/, int64_t n, const uint8_t* payload, int64_t payload_bytes, int steps,
+                         uint8_t* mask /*[dev n]*/, int64_t* host2, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- backward pass of the training graph (trainer.py:127-134 `sum_loss.backward()`; csrc/grad.hip).  None of this is on the encode/decode
  *      path.  No floating-point atomics: every reduction has a fixed order (per-workgroup partials in `workspace`, added in ascending
  *      workgroup order by a second stage) and every grid is a function of the shapes alone, so gradients are bitwise reproducible.

@@ -630,6 +630,8 @@ def _parse_cli(argv):
     p.add_argument("--lossless", action='store_true',
                    help="also write _O.bin, the occupancy stream of the lossless mode (lossless.py): encode, decode, check that the decoded "
                         "voxel set is the input's, print the bpp of each file")
+    p.add_argument("--occupancy_coder", choices=('host', 'device'), default='host',
+                   help="with --lossless: who codes _O.bin, the host range coder (version 1) or interleaved rANS on the device (version 2)")
     return p.parse_args(argv)
 
 
@@ -666,7 +668,7 @@ def main(argv=None):
     args = _parse_cli(argv)
     if args.lossless:
         from . import lossless
-        lossless.run(args.ckptdir, args.filedir, args.outdir)
+        lossless.run(args.ckptdir, args.filedir, args.outdir, occupancy_coder=args.occupancy_coder)
         return
     with _Stopwatch('Loading Time', 4, sync=False):
         x = load_sparse_tensor(args.filedir, device)

@@ -14,7 +14,19 @@ the same two functions below (`_latent_level`, `_logits`).
                                                          order, symbol i under CDF row ctx[i]
 Level l + 1's contexts need level l decoded, so the payloads are separate streams.
 
-    python -m pcgcv2_amd.lossless --ckptdir CKPT --filedir CLOUD.ply [--outdir DIR]
+Version 2 (`occupancy_coder='device'`) keeps the head and the table and codes each payload ON THE DEVICE by interleaved rANS
+(csrc/occupancy_rans.hip; the layout is in include/pcgc_hip.h): the context words never leave the device, the decoded bits never reach the
+host, only the coded bytes cross the bus.  A payload is cut into chunks of 64 x S rows, one wave each; every chunk costs up to 64 x 64 + 32
+bits beyond its ideal length, so S (`chunk_steps`, recorded in the stream) trades rate against parallelism.  `decode` reads either version
+whatever the constructor said.
+
+Integrity.  A version-1 payload is decoded and coded again, and must give the same bytes: every cut, extended or damaged stream is
+refused.  Version 2 has the check rANS offers: per chunk, the stored states must lie in [2^31, 2^63), exactly the declared number of words
+must be consumed and all 64 lanes must end at their initial state 2^31.  The tables' lengths are checked against the file, so cuts and
+extensions are refused; damage inside a chunk's words escapes when the lanes that read it still end at 2^31 with the word count intact —
+unlikely (a damaged lane has to land on one value of 2^32 and more), not impossible.  A decoder that needs certainty asks for version 1.
+
+    python -m pcgcv2_amd.lossless --ckptdir CKPT --filedir CLOUD.ply [--outdir DIR] [--occupancy_coder {host,device}] [--chunk_steps S]
 """
 import os
 import struct
@@ -31,15 +43,25 @@ from .sparse import CoordMap, SparseTensor, require_gpu
 
 SUFFIX = '_O.bin'
 MAGIC, VERSION = b'PCGL', 1
+VERSION_DEVICE = 2                                # payloads coded by ops.occ_rans_encode
+CODERS = {'host': VERSION, 'device': VERSION_DEVICE}
+CHUNK_STEPS = 4096                                # S of a version-2 payload unless the caller says otherwise
 _HEAD = struct.Struct('<4sII')
 _LEVELS = struct.Struct('<6Q')                    # (rows, bytes) of the three levels
 LEVELS = 3
 
 
 class LosslessCoder():
-    """Coder(model, filename) plus the occupancy stream.  One frame per call."""
+    """Coder(model, filename) plus the occupancy stream.  One frame per call.  occupancy_coder: 'host' writes version 1 (the host range
+    coder), 'device' version 2 (rANS on the device) in chunks of 64 x chunk_steps rows (None: CHUNK_STEPS; 0: one chunk per level)."""
 
-    def __init__(self, model, filename):
+    def __init__(self, model, filename, occupancy_coder='host', chunk_steps=None):
+        if occupancy_coder not in CODERS:
+            raise ValueError(f'occupancy_coder {occupancy_coder!r}: one of {sorted(CODERS)}')
+        self.occupancy_coder = occupancy_coder
+        self.chunk_steps = CHUNK_STEPS if chunk_steps is None else int(chunk_steps)
+        if not 0 <= self.chunk_steps <= ops.RANS_MAX_STEPS:
+            raise ValueError(f'chunk_steps {chunk_steps}: 0 (one chunk per level) or 1 .. 2^24')
         self.model = model
         self.filename = filename
         self.coder = Coder(model, filename)
@@ -102,26 +124,39 @@ class LosslessCoder():
         min_v, _, sym_h = ops.quantize_symbols(y.F)
         out = self._latent_level(torch.from_numpy(sym_h).to(dev), min_v, y.C)
         t = self._tick('copies', t, dev)
-        rows, units, payloads = [], 0, []
+        rows, units, payloads, chunks = [], 0, [], []
+        on_device = code and self.occupancy_coder == 'device'
         for l in range(LEVELS):
             out, logits = self._logits(out, l)
             truth = isin_mask(out.cmap.C, truths[l])
             t = self._tick('network', t, dev)
             packed, sums = ops.occ_symbols(logits, truth)
             t = self._tick('k_occ_symbols', t, dev)
-            words, occupied, cost = ops.occ_words_host(packed, sums)
-            t = self._tick('copies', t, dev)
+            candidates = packed.shape[0]
+            if on_device:                         # the words stay on the device; the counts come with the payload's length
+                steps = self.chunk_steps or max(1, ops.occ_rans_chunks(candidates, 1))
+                payload, occupied, cost = ops.occ_rans_encode(packed, steps, sums)
+                chunks.append(ops.occ_rans_chunks(candidates, steps))
+                t = self._tick('k_occ_rans_encode', t, dev)
+            else:
+                words, occupied, cost = ops.occ_words_host(packed, sums)
+                t = self._tick('copies', t, dev)
             if occupied != len(truths[l]):
-                raise PcgcError(f'lossless encode: level {l} holds {len(truths[l])} voxels but {occupied} of its {len(words)} candidates are '
+                raise PcgcError(f'lossless encode: level {l} holds {len(truths[l])} voxels but {occupied} of its {candidates} candidates are '
                                 'among them: the input is not a set of distinct voxels of one frame')
-            rows.append(len(words))
+            rows.append(candidates)
             units += cost
-            if code:
+            if on_device:
+                payloads.append(payload)
+            elif code:
                 payloads.append(ops.rc_encode_ctx(self._cdf, words >> 1, words & 1))
                 t = self._tick('host coder', t)
             out = self.model.decoder.pruning(out, truth, n_keep=occupied)
             t = self._tick('network', t, dev)
-        return {'est_units_O': units, 'est_bits_O': units / occupancy_model.COST_UNIT, 'rows': rows}, payloads
+        record = {'est_units_O': units, 'est_bits_O': units / occupancy_model.COST_UNIT, 'rows': rows}
+        if on_device:
+            record['chunks'] = chunks
+        return record, payloads
 
     @torch.no_grad()
     def encode(self, x, postfix=''):
@@ -134,7 +169,7 @@ class LosslessCoder():
             record, payloads = self._enhance(x, y, code=True)
             t = self._tick(None, 0.0)
             sizes = [v for r, p in zip(record['rows'], payloads) for v in (r, len(p))]
-            blob = _HEAD.pack(MAGIC, VERSION, occupancy_model.table_crc()) + _LEVELS.pack(*sizes) + b''.join(payloads)
+            blob = _HEAD.pack(MAGIC, CODERS[self.occupancy_coder], occupancy_model.table_crc()) + _LEVELS.pack(*sizes) + b''.join(payloads)
             _dump(self.filename + postfix + SUFFIX, blob)
             self._tick('host coder', t)
         record['bits_O'] = 8 * len(blob)
@@ -155,6 +190,11 @@ class LosslessCoder():
 
     # ---- decoder ------------------------------------------------------------------------------------------------------------------------
     def _read_stream(self, postfix):
+        """-> (candidate rows, payloads) of the three levels, of either version"""
+        return self._read_versioned(postfix)[1:]
+
+    def _read_versioned(self, postfix):
+        """-> (version, candidate rows, payloads); a version-2 payload's head and tables are checked against its rows and size here"""
         path = self.filename + postfix + SUFFIX
         blob = _slurp(path)
         if len(blob) < _HEAD.size + _LEVELS.size:
@@ -162,8 +202,8 @@ class LosslessCoder():
         magic, version, crc = _HEAD.unpack_from(blob, 0)
         if magic != MAGIC:
             raise PcgcError(f'{path}: not an occupancy stream (magic {magic!r})')
-        if version != VERSION:
-            raise PcgcError(f'{path}: version {version}; this decoder reads version {VERSION}')
+        if version not in CODERS.values():
+            raise PcgcError(f'{path}: version {version}; this decoder reads versions {sorted(CODERS.values())}')
         if crc != occupancy_model.table_crc():
             raise PcgcError(f'{path}: coded with other probability tables (CRC-32 {crc:08x}, here {occupancy_model.table_crc():08x})')
         sizes = _LEVELS.unpack_from(blob, _HEAD.size)
@@ -171,19 +211,28 @@ class LosslessCoder():
         if len(blob) != _HEAD.size + _LEVELS.size + sum(nbytes):
             raise PcgcError(f'{path}: {len(blob)} bytes, but the header declares payloads of {list(nbytes)} bytes')
         offs = np.cumsum([_HEAD.size + _LEVELS.size] + list(nbytes))
-        return rows, [blob[offs[l]:offs[l + 1]] for l in range(LEVELS)]
+        payloads = [blob[offs[l]:offs[l + 1]] for l in range(LEVELS)]
+        if version == VERSION_DEVICE:
+            for l in range(LEVELS):
+                try:
+                    ops.occ_rans_layout(payloads[l], rows[l])
+                except PcgcError as e:
+                    raise PcgcError(f'{path}: level {l}: {e}') from None
+        return version, rows, payloads
 
     @torch.no_grad()
     def decode(self, postfix=''):
-        """reads `_C.bin`, `_F.bin`, `_H.bin` and `_O.bin` -> the stride-1 sparse tensor whose coordinate set is the input's.  Raises
-        PcgcError on a stream that is damaged, cut, extended or inconsistent; never returns a cloud from one."""
+        """reads `_C.bin`, `_F.bin`, `_H.bin` and `_O.bin` (either version) -> the stride-1 sparse tensor whose coordinate set is the
+        input's.  Raises PcgcError on a stream that is cut, extended or inconsistent.  A version-1 stream with damaged payload bytes is
+        always refused, never decoded to a cloud; a version-2 stream is refused when a chunk fails its check (the module docstring says
+        what that check can and cannot see)."""
         dev = require_gpu(next(self.model.decoder.parameters()).device)
         with torch.cuda.device(dev):
             return self._decode(postfix, dev)
 
     def _decode(self, postfix, dev):
         t = self._tick(None, 0.0, dev)
-        rows, payloads = self._read_stream(postfix)
+        version, rows, payloads = self._read_versioned(postfix)
         fc = self.coder.feature_coder
         sym_h, min_v = fc.decode_symbols(postfix=postfix, device=dev)
         lvl8 = self.coder._decode_geometry(postfix, dev, torch.cuda.current_stream(dev))
@@ -199,15 +248,22 @@ class LosslessCoder():
             t = self._tick('network', t, dev)
             packed, _ = ops.occ_symbols(logits)
             t = self._tick('k_occ_symbols', t, dev)
-            words, _, _ = ops.occ_words_host(packed, None)
-            t = self._tick('copies', t, dev)
-            bits = ops.rc_decode_ctx(self._cdf, words >> 1, payloads[l])
-            t = self._tick('host coder', t)
-            parents = int(bits.sum())
+            if version == VERSION_DEVICE:         # the bits never reach the host: the mask is the kernel's
+                try:
+                    mask, parents = ops.occ_rans_decode(packed, payloads[l], rows[l])
+                except PcgcError as e:
+                    raise PcgcError(f'{self.filename + postfix + SUFFIX}: level {l}: {e}') from None
+                t = self._tick('k_occ_rans_decode', t, dev)
+            else:
+                words, _, _ = ops.occ_words_host(packed, None)
+                t = self._tick('copies', t, dev)
+                bits = ops.rc_decode_ctx(self._cdf, words >> 1, payloads[l])
+                t = self._tick('host coder', t)
+                parents = int(bits.sum())
+                mask = torch.from_numpy(bits.astype(np.uint8)).to(dev)
+                t = self._tick('copies', t, dev)
             if parents == 0:
                 raise PcgcError(f'{self.filename + postfix + SUFFIX}: level {l} decodes to no voxel at all')
-            mask = torch.from_numpy(bits.astype(np.uint8)).to(dev)
-            t = self._tick('copies', t, dev)
             out = self.model.decoder.pruning(out, mask, n_keep=parents)
             t = self._tick('network', t, dev)
         return out
@@ -227,7 +283,7 @@ def same_voxels(a, b):
 
 
 # ------------------------------------------------------------------------------------------------ CLI
-def run(ckptdir, filedir, outdir):
+def run(ckptdir, filedir, outdir, occupancy_coder='host', chunk_steps=None):
     """encode, decode, check set equality, print the bpp of each file and the total"""
     from .coder import device, _Stopwatch
     from .data_utils import load_sparse_tensor, write_ply_ascii_geo
@@ -241,7 +297,7 @@ def run(ckptdir, filedir, outdir):
     model = PCCModel().to(device)
     model.load_state_dict(torch.load(ckptdir, map_location=device)['model'])
     print('load checkpoint from \t', ckptdir)
-    coder = LosslessCoder(model=model, filename=prefix)
+    coder = LosslessCoder(model=model, filename=prefix, occupancy_coder=occupancy_coder, chunk_steps=chunk_steps)
     with _Stopwatch('Enc Time'):
         record = coder.encode(x)
     with _Stopwatch('Dec Time'):
@@ -267,8 +323,12 @@ def main(argv=None):
     p.add_argument("--ckptdir", default='ckpts/r3_0.10bpp.pth')
     p.add_argument("--filedir", default='../../../testdata/8iVFB/longdress_vox10_1300.ply')
     p.add_argument("--outdir", default='./output')
+    p.add_argument("--occupancy_coder", choices=sorted(CODERS), default='host',
+                   help="who codes _O.bin: the host range coder (version 1) or interleaved rANS on the device (version 2)")
+    p.add_argument("--chunk_steps", type=int, default=None,
+                   help="device coder: rows per chunk / 64 (0: one chunk per level); default lossless.CHUNK_STEPS")
     args = p.parse_args(argv)
-    run(args.ckptdir, args.filedir, args.outdir)
+    run(args.ckptdir, args.filedir, args.outdir, args.occupancy_coder, args.chunk_steps)
 
 
 if __name__ == '__main__':

@@ -1569,6 +1569,79 @@ def occ_tables():
     return p1, cost
 
 
+# ------------------------------------------------------------------------------------------------ lossless mode, device coder (csrc/occupancy_rans.hip)
+RANS_LANES = 64
+RANS_MAX_STEPS = 1 << 24
+
+
+def occ_rans_chunks(n, steps):
+    """chunks of 64 x steps rows that n rows make"""
+    return -(-int(n) // (RANS_LANES * int(steps)))
+
+
+def _rans_ws(n, steps, dev):
+    nbytes = int(lib().pcgc_occ_rans_workspace_bytes(n, steps))
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev), nbytes
+
+
+def occ_rans_encode(packed, steps, sums=None):
+    """packed int16 [n] as occ_symbols returns it -> the level's payload of `_O.bin` version 2 (include/pcgc_hip.h) as bytes, coded on the
+    device in chunks of 64 x steps rows.  One small synchronising copy (the length) and one copy of the finished payload.  With sums
+    (occ_symbols' second result) the small copy brings them along: -> (bytes, occupied rows, ideal code length in 2^-16 bit)."""
+    n, dev, steps = _dev(packed, torch.int16, 'packed').shape[0], packed.device, int(steps)
+    if packed.dim() != 1 or not 1 <= steps <= RANS_MAX_STEPS:
+        raise PcgcError(f'occ_rans_encode: packed {tuple(packed.shape)}, {steps} steps per chunk (1 .. 2^24)')
+    if sums is not None and (_dev(sums, torch.int64, 'sums').numel() != 2):
+        raise PcgcError('occ_rans_encode: sums is occ_symbols\' int64 [2]')
+    cap = 8 + 516 * occ_rans_chunks(n, steps) + 4 * n
+    out = torch.empty((cap + 7) // 8, dtype=torch.int64, device=dev)
+    ws, ws_bytes = _rans_ws(n, steps, dev)
+    host = np.zeros(3, dtype=np.int64)
+    check(lib().pcgc_occ_rans_encode(_p(packed), n, steps, _p(sums), _p(out), cap, host.ctypes.data, _p(ws), ws_bytes, _stream(packed)), 'occ_rans_encode')
+    payload = out.view(torch.uint8)[:int(host[0])].cpu().numpy().tobytes()
+    return payload if sums is None else (payload, int(host[1]), int(host[2]))
+
+
+def occ_rans_layout(payload, n):
+    """the host's checks of one level's payload of `_O.bin` version 2 against its n rows and its own size -> (S, K).  PcgcError when S is
+    outside 1 .. 2^24, K is not ceil(n / (64 S)), the tables do not fit or the word counts do not add up to the byte length."""
+    if len(payload) < 8:
+        raise PcgcError(f'occ_rans: {len(payload)} bytes, shorter than the head')
+    steps, chunks = (int(v) for v in np.frombuffer(payload, '<u4', 2))
+    if not 1 <= steps <= RANS_MAX_STEPS:
+        raise PcgcError(f'occ_rans: {steps} steps per chunk (1 .. 2^24)')
+    if chunks != occ_rans_chunks(n, steps):
+        raise PcgcError(f'occ_rans: {chunks} chunks declared; {n} rows in chunks of 64 x {steps} make {occ_rans_chunks(n, steps)}')
+    if len(payload) < 8 + 516 * chunks:
+        raise PcgcError(f'occ_rans: {len(payload)} bytes, cut inside the tables of {chunks} chunks')
+    words = int(np.frombuffer(payload, '<u4', chunks, 8 + 512 * chunks).astype(np.int64).sum())
+    if 8 + 516 * chunks + 4 * words != len(payload):
+        raise PcgcError(f'occ_rans: {len(payload)} bytes, but the chunks declare {words} words in all')
+    return steps, chunks
+
+
+def occ_rans_decode(packed, payload, n):
+    """packed int16 [n]: the contexts (occ_symbols without truth); payload: bytes of one level of `_O.bin` version 2 -> (uint8 mask [n] on
+    the device, occupied rows).  The payload goes up in one copy, the two numbers come back in one.  PcgcError on a payload whose S, K or
+    lengths disagree with n and its own size (checked here, before any launch) and on an unsound chunk (the kernel's verdict)."""
+    n, dev = int(n), packed.device
+    if _dev(packed, torch.int16, 'packed').dim() != 1 or packed.shape[0] != n:
+        raise PcgcError(f'occ_rans_decode: packed {tuple(packed.shape)} for {n} rows')
+    payload = bytes(payload)
+    steps, chunks = occ_rans_layout(payload, n)
+    up = torch.frombuffer(bytearray(payload) + bytes(-len(payload) % 8), dtype=torch.int64).to(dev)        # (8-byte aligned on the device)
+    mask = torch.empty(n, dtype=torch.uint8, device=dev)
+    ws_bytes = 32 + (chunks + 1) // 2 * 8                                          # (the slot + K offsets; no scratch on this side)
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    host = np.zeros(2, dtype=np.int64)
+    check(lib().pcgc_occ_rans_decode(_p(packed), n, _p(up), len(payload), steps, _p(mask), host.ctypes.data, _p(ws), ws_bytes, _stream(packed)),
+          'occ_rans_decode')
+    if host[1]:
+        raise PcgcError(f'occ_rans_decode: unsound payload ({int(host[1])} of {chunks} chunks fail their check: states in [2^31, 2^63), '
+                        'exactly W_k words consumed, every lane back at 2^31)')
+    return mask, int(host[0])
+
+
 # ------------------------------------------------------------------------------------------------ backward pass (csrc/grad.hip)
 def conv_wgrad_rows_per_group(K, n_rows, Cin, Cout):
     """consecutive rows one workgroup of conv_wgrad reduces (a function of the shapes alone)"""

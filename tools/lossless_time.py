@@ -3,9 +3,11 @@
 this fresh process: the median of --repeat runs end to end, next to one lossy Coder.encode + decode pair in the same process, and — from a
 second set of runs with a device synchronisation between the phases — the split into network, k_occ_symbols, host coder and copies.
 Also: candidate rows per level, bits of `_O.bin` against its ideal length, bpp (synthetic weights: says nothing about trained models), and
-the gap between the ideal length and loss.get_bce on the same forward point.  With --trace it re-runs itself once under
-`rocprofv3 --kernel-trace --stats` (a fresh child process) and prints the k_occ_* rows.
-    tools/lossless_time.py [--cloud NAME] [--repeat K] [--trace]"""
+the gap between the ideal length and loss.get_bce on the same forward point.  Both forms of `_O.bin` are timed in this one process: the host
+range coder (version 1) and rANS on the device (version 2, phases k_occ_rans_encode / k_occ_rans_decode) in chunks of 64 x --chunk_steps rows;
+--occupancy_coder says which of the two fills the top-level figures (and the --trace run), the other is reported under `other_coder`.
+With --trace it re-runs itself once under `rocprofv3 --kernel-trace --stats` (a fresh child process) and prints the k_occ_* rows.
+    tools/lossless_time.py [--cloud NAME] [--repeat K] [--occupancy_coder {host,device}] [--chunk_steps S[,S..]] [--trace]"""
 import argparse, csv, glob, json, os, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -13,6 +15,9 @@ sys.path.insert(0, ROOT)
 ap = argparse.ArgumentParser()
 ap.add_argument('--cloud', default='shell10')
 ap.add_argument('--repeat', type=int, default=7)
+ap.add_argument('--occupancy_coder', choices=('host', 'device'), default='device')
+ap.add_argument('--chunk_steps', default='', help='S of the device coder (0: one chunk per level); a comma-separated list adds a table of '
+                'medians and sizes over these values; default: lossless.CHUNK_STEPS')
 ap.add_argument('--trace', action='store_true', help='also one rocprofv3 --kernel-trace --stats run of two encode + decode pairs (child process)')
 ap.add_argument('--one-call', action='store_true', help=argparse.SUPPRESS)
 args = ap.parse_args()
@@ -21,7 +26,7 @@ args = ap.parse_args()
 def trace_table():
     with tempfile.TemporaryDirectory() as d:
         cmd = ['rocprofv3', '--kernel-trace', '--stats', '--output-format', 'csv', '-d', d, '--', sys.executable, os.path.abspath(__file__),
-               '--cloud', args.cloud, '--one-call']
+               '--cloud', args.cloud, '--occupancy_coder', args.occupancy_coder, '--chunk_steps', args.chunk_steps, '--one-call']
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         if r.returncode != 0:
             raise SystemExit('rocprofv3 failed:\n' + r.stderr[-2000:])
@@ -50,7 +55,11 @@ coords = torch.cat([torch.zeros((len(pts), 1), dtype=torch.int32, device=dev), p
 x = SparseTensor(torch.ones((len(pts), 1), device=dev), coordinates=coords, tensor_stride=1, device=dev)
 tmp = tempfile.TemporaryDirectory()
 prefix = os.path.join(tmp.name, 'frame')
-exact, lossy = lossless.LosslessCoder(model, prefix), Coder(model, prefix + '_lossy')
+steps_list = [int(v) for v in args.chunk_steps.split(',') if v != ''] or [None]
+coders = {'host': lossless.LosslessCoder(model, prefix + '_host'),
+          'device': lossless.LosslessCoder(model, prefix + '_device', occupancy_coder='device', chunk_steps=steps_list[0])}
+other = 'host' if args.occupancy_coder == 'device' else 'device'
+exact, lossy = coders[args.occupancy_coder], Coder(model, prefix + '_lossy')
 
 if args.one_call:
     for _ in range(2):
@@ -67,13 +76,14 @@ def median_ms(fn, runs):
     return round(float(np.median(times)) * 1e3, 3)
 
 
-def phases_ms(fn, runs):
+def phases_ms(fn, runs, coder=None):
+    coder = coder or exact
     out = []
     for _ in range(runs):
-        exact.times = {}
+        coder.times = {}
         fn(); torch.cuda.synchronize()
-        out.append(exact.times)
-    exact.times = None
+        out.append(coder.times)
+    coder.times = None
     return {k: round(float(np.median([o.get(k, 0.0) for o in out])) * 1e3, 3) for k in out[0]}
 
 
@@ -83,10 +93,28 @@ out = exact.decode()
 report = {'cloud': args.cloud, 'points': len(pts), 'runs': runs, 'weights': 'synthetic (the rate says nothing about trained models)',
           'exact': lossless.same_voxels(out.C, x.C), 'candidate_rows': record['rows'],
           'bits_O': record['bits_O'], 'ideal_bits_O': round(record['est_bits_O'], 1), 'bpp_O': round(record['bits_O'] / len(pts), 4),
-          'bpp_lossy_files': round(float(stream_bits(prefix).sum()) / len(pts), 4)}
+          'bpp_lossy_files': round(float(stream_bits(exact.filename).sum()) / len(pts), 4),
+          'occupancy_coder': args.occupancy_coder, 'chunk_steps': coders['device'].chunk_steps, 'chunks': record.get('chunks')}
 report['median_ms'] = {'lossless_encode': median_ms(lambda: exact.encode(x), runs), 'lossless_decode': median_ms(exact.decode, runs),
                        'lossy_encode': median_ms(lambda: lossy.encode(x), runs), 'lossy_decode': median_ms(lossy.decode, runs)}
 report['phases_ms_synchronised'] = {'encode': phases_ms(lambda: exact.encode(x), runs), 'decode': phases_ms(exact.decode, runs)}
+second = coders[other]
+second_record = second.encode(x)
+report['other_coder'] = {'occupancy_coder': other, 'exact': lossless.same_voxels(second.decode().C, x.C), 'bits_O': second_record['bits_O'],
+                         'chunks': second_record.get('chunks'),
+                         'median_ms': {'lossless_encode': median_ms(lambda: second.encode(x), runs), 'lossless_decode': median_ms(second.decode, runs)},
+                         'phases_ms_synchronised': {'encode': phases_ms(lambda: second.encode(x), runs, second),
+                                                    'decode': phases_ms(second.decode, runs, second)}}
+if len(steps_list) > 1:                                               # the S table: medians and size of `_O.bin` per chunk_steps
+    table = []
+    for steps in steps_list:
+        c = lossless.LosslessCoder(model, prefix + '_steps', occupancy_coder='device', chunk_steps=steps)
+        r = c.encode(x)
+        table.append({'chunk_steps': steps, 'chunks': r['chunks'], 'bits_O': r['bits_O'], 'exact': lossless.same_voxels(c.decode().C, x.C),
+                      'lossless_encode_ms': median_ms(lambda: c.encode(x), runs), 'lossless_decode_ms': median_ms(c.decode, runs),
+                      'k_occ_rans_encode_ms': phases_ms(lambda: c.encode(x), runs, c).get('k_occ_rans_encode'),
+                      'k_occ_rans_decode_ms': phases_ms(c.decode, runs, c).get('k_occ_rans_decode')})
+    report['chunk_steps_table'] = table
 
 # the same forward point through loss.get_bce: teacher forcing by the truth alone, BCE of every level's logits in bits
 with torch.no_grad():
