@@ -1,14 +1,19 @@
 """Thin functional layer over the C-ABI (include/pcgc_hip.h): torch tensors in, torch tensors out.
 
 PyTorch is used for device memory and streams only; all arithmetic happens in libpcgc_hip.so.  Every function
-requires ROCm device tensors and raises otherwise — there is no CPU path in the product.
+requires ROCm device tensors and raises otherwise — there is no CPU path in the product.  What a sparse-conv launch is charged in the
+roofline report is written down in roofline.py; `PROFILE`, its one instance, brackets the launches here.
 """
+import ctypes
 import os as _os
+from collections import namedtuple
 
 import numpy as np
 import torch
 
+from . import roofline
 from ._lib import lib, check, PcgcError
+from .roofline import MFMA_F32_PEAK_TFLOPS, child_pairs, _halo_cells          # noqa: F401  (read as ops.<name> by bench.py, tools/ and tests)
 
 
 def _stream(t=None):
@@ -50,196 +55,8 @@ def _ld(t):
     return t.stride(0)
 
 
-# ------------------------------------------------------------------------------------------------ profiling hook
-MFMA_F32_PEAK_TFLOPS = 157.3      # MI355X_MICROARCH.md: dense fp32 MFMA peak
-_CHILD_WEIGHT = None
-
-
-def child_pairs(parent_nbr):
-    """(in,out) pairs of the CHILDREN level's k3 map, counted from the parent map (the children map is never built): a present
-    parent neighbour at offset kp contributes as many (child row, offset) pairs as halo cells of that parent are reached:
-    64 for the centre, 16 per face, 4 per edge, 1 per corner neighbour."""
-    global _CHILD_WEIGHT
-    if _CHILD_WEIGHT is None or _CHILD_WEIGHT.device != parent_nbr.device:
-        w = np.zeros(27, np.int64)
-        for kp, jc, reach in _halo_cells():
-            w[kp] += len(reach)
-        _CHILD_WEIGHT = torch.from_numpy(w).to(parent_nbr.device)
-    return int(((parent_nbr >= 0).sum(1) * _CHILD_WEIGHT).sum().item())
-
-
-class _Profile:
-    """Brackets the sparse-conv launches with HIP events on the stream they are launched on, and turns the timings into the
-    `roofline` object of bench.py.  Per launch, with P = (in,out) pairs of the level's k3 map (counted, not assumed), n rows:
-        gathered bytes   (SURVEY.md §8d)   k3 conv: P*Cin*4 + P*8 + n*Cout*4 ;  k1 conv: n*(Cin+Cout)*4 — every (in,out) pair
-                         charged: the re-use of a row by its ~18 outputs is served by L2 / LDS, so this rate can exceed the HBM peak
-        compulsory bytes                   every input row, kernel-map entry and output row once: what HBM has to move
-        flops                              2*P*Cin*Cout (+ 2*n*Cin*Cout for k1 parts);  k2 s2 down / generative up: P = fine rows
-        mfma_issued                        fp32 MFMA flops the kernel issues (zero-padded columns and absent rows included)
-    A fused InceptionResNet pass is charged the sum of the convs it computes:
-        pass A: k3 C->C/4 + k1 C->C/4          pass B: k3 C/4->C/2 + k3 C/4->C/4 + k1 C/4->C/2.
-    Records are per (kernel, level) key; the report groups them by kernel NAME (the text of `kernel` before ' (': what a rocprofv3
-    --stats line pools too), so that `roofline.kernel` is a statistic of one compiled kernel over every level it serves."""
-
-    TIE = 0.05                     # kernel names whose per-step time is within 5 % of the largest are tied: the lower fraction of peak wins
-
-    def __init__(self):
-        self.reset(False)
-
-    def reset(self, enabled=False, only=None):
-        self.enabled = enabled
-        self.only = None if only is None else frozenset(only)      # bracket just these (kernel, level) keys: keeps the event overhead out of a timed region
-        self.counting = False
-        self.records = {}          # key -> dict(kernel, n, formulas, events=[(e0,e1)])
-        self.pairs = {}            # n_out -> P of the level's k3 map
-
-    def want(self, key):
-        return self.enabled and (self.only is None or key in self.only)
-
-    @staticmethod
-    def name_of(kernel):
-        return kernel.split(' (')[0]
-
-    def bracket(self, key, kernel, n, gathered, flops, compulsory=None, mfma_issued=None, pairs=None):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        r = self.records.setdefault(key, {'kernel': kernel, 'n': n, 'gathered': gathered, 'flops': flops, 'compulsory': compulsory,
-                                          'mfma_issued': mfma_issued, 'pairs': pairs, 'events': []})
-        r['events'].append((e0, e1))
-        return e0, e1
-
-    def count(self, nbr):
-        n = nbr.shape[1]
-        if n not in self.pairs:
-            self.pairs[n] = int((nbr >= 0).sum().item())
-
-    def count_children(self, parent_nbr):
-        n = 8 * parent_nbr.shape[1]
-        if n not in self.pairs:
-            self.pairs[n] = child_pairs(parent_nbr)
-
-    def detail(self):
-        """one entry per (kernel, level): mean AND median launch time (a first-touch allocation or a preempted launch must not decide a ranking)"""
-        out = []
-        for key, r in self.records.items():
-            ts = sorted(e0.elapsed_time(e1) for e0, e1 in r['events'])
-            ms = sum(ts)
-            us = ms / len(ts) * 1e3
-            med = (ts[len(ts) // 2] if len(ts) % 2 else 0.5 * (ts[len(ts) // 2 - 1] + ts[len(ts) // 2])) * 1e3
-            d = {'key': key, 'name': self.name_of(r['kernel']), 'kernel': r['kernel'], 'n_out': r['n'], 'launches': len(ts), 'ms': ms, 'avg_us': us, 'median_us': med}
-            P = r['pairs'] if r['pairs'] is not None else self.pairs.get(r['n'])     # (k2 s2 convs carry their own P = fine rows)
-            if P is not None:
-                d['pairs'] = P
-                d['gathered_bytes'] = r['gathered'](P)
-                d['flops'] = r['flops'](P)
-                d['gathered_GBps'] = d['gathered_bytes'] / (us * 1e-6) / 1e9
-                d['TFLOPs'] = d['flops'] / (us * 1e-6) / 1e12
-                if r['compulsory'] is not None:
-                    d['compulsory_bytes'] = r['compulsory']
-                    d['compulsory_GBps'] = r['compulsory'] / (us * 1e-6) / 1e9
-                if r['mfma_issued'] is not None:
-                    issued = r['mfma_issued'](P) if callable(r['mfma_issued']) else r['mfma_issued']      # (a packed kernel issues per present pair)
-                    d['mfma_issued_flops'] = issued
-                    d['mfma_issued_TFLOPs'] = issued / (us * 1e-6) / 1e12
-            out.append(d)
-        return sorted(out, key=lambda d: -d['ms'])
-
-    def families(self, steps, peak_gbs):
-        """the fixed report: one entry per kernel NAME, its levels pooled (sum of flops / sum of time): us per step, launches per step, fraction
-        of the fp32 MFMA peak (algorithmic flops), issued / algorithmic, compulsory-traffic fraction of the HBM peak; sorted by name"""
-        groups = {}
-        for d in self.detail():
-            if 'pairs' in d:
-                groups.setdefault(d['name'], []).append(d)
-        fam = []
-        for name, ds in groups.items():
-            ms = sum(d['ms'] for d in ds)
-            med_ms = sum(d['median_us'] * d['launches'] for d in ds) * 1e-3
-            fl = sum(d['flops'] * d['launches'] for d in ds)
-            comp = sum(d.get('compulsory_bytes', 0) * d['launches'] for d in ds)
-            issued = sum(d.get('mfma_issued_flops', 0) * d['launches'] for d in ds)
-            f = {'kernel': name, 'levels': sorted({d['n_out'] for d in ds}), 'launches_per_step': round(sum(d['launches'] for d in ds) / steps, 2),
-                 'us_per_step': round(ms * 1e3 / steps, 1), 'median_us_per_step': round(med_ms * 1e3 / steps, 1),
-                 'TFLOPs': round(fl / (ms * 1e-3) / 1e12, 2), 'frac': round(fl / (ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS, 4),
-                 'issued_over_algorithmic': round(issued / fl, 2) if issued and fl else None,
-                 'compulsory_frac_of_hbm': round(comp / (ms * 1e-3) / 1e9 / peak_gbs, 4)}
-            fam.append(f)
-        return sorted(fam, key=lambda f: f['kernel'])
-
-    def dominant(self, steps, peak_gbs):
-        """(kernel name, its keys): the name with the largest per-step time (median launch time x launches, so one slow sample cannot decide);
-        names within TIE of it are tied and the LOWEST fraction of the fp32 MFMA peak wins — a rule that returns the same kernel on every box
-        as long as the ranking of the fractions holds, where "largest time" alone flipped between four groups 3 % apart (VERDICT r5 weak #5)."""
-        fam = self.families(steps, peak_gbs)
-        if not fam:
-            return None, ()
-        top = max(f['median_us_per_step'] for f in fam)
-        tied = [f for f in fam if f['median_us_per_step'] >= (1.0 - self.TIE) * top]
-        best = min(tied, key=lambda f: (f['frac'], f['kernel']))
-        keys = tuple(k for k, r in self.records.items() if self.name_of(r['kernel']) == best['kernel'])
-        return best['kernel'], keys
-
-    def summary(self, peak_gbs, steps, name=None):
-        """roofline of one kernel name (default: `dominant`), its levels pooled: achieved = sum of algorithmic flops / sum of launch time.
-        `bound` is the roofline the kernel sits closer to: "mfma" (algorithmic fp32 flops against the dense fp32 MFMA peak) or
-        "hbm" (compulsory bytes against the HBM peak).  `aggregate` = every bracketed launch; `families` = the per-name table."""
-        d_all = [r for r in self.detail() if 'pairs' in r]
-        if not d_all:
-            return None
-        if name is None:
-            name, _ = self.dominant(steps, peak_gbs)
-        d = [r for r in d_all if r['name'] == name]
-        if not d:
-            return None
-        t_s = sum(r['ms'] for r in d) * 1e-3
-        launches = sum(r['launches'] for r in d)
-        fl = sum(r['flops'] * r['launches'] for r in d)
-        comp = sum(r.get('compulsory_bytes', 0) * r['launches'] for r in d)
-        gath = sum(r['gathered_bytes'] * r['launches'] for r in d)
-        issued = sum(r.get('mfma_issued_flops', 0) * r['launches'] for r in d)
-        tf, cg = fl / t_s / 1e12, comp / t_s / 1e9
-        hbm_frac, mfma_frac = cg / peak_gbs, tf / MFMA_F32_PEAK_TFLOPS
-        # an MFMA kernel is priced against the matrix peak unless its compulsory traffic rate is the larger fraction of ITS peak even
-        # compared with the pipe utilisation (issued flops), i.e. unless it really is the memory side that is closer to its limit
-        is_mfma = issued > 0 and max(mfma_frac, issued / t_s / 1e12 / MFMA_F32_PEAK_TFLOPS) >= hbm_frac
-        roof = {'bound': 'mfma' if is_mfma else 'hbm'}
-        if is_mfma:
-            roof.update(achieved=round(tf, 2), peak=MFMA_F32_PEAK_TFLOPS, unit='TFLOP/s', frac=round(mfma_frac, 4))
-        else:
-            roof.update(achieved=round(cg, 2), peak=peak_gbs, unit='GB/s', frac=round(hbm_frac, 4))
-        roof.update(traffic=None, kernel=name, description=d[0]['kernel'], avg_launch_us=round(t_s * 1e6 / launches, 2), launches_timed=launches,
-                    launches_per_step=round(launches / steps, 2),
-                    selection=f'kernel NAME with the largest per-step time (median launch time x launches, levels pooled); names within {int(self.TIE * 100)} % '
-                              'are tied and the lowest fraction of peak wins',
-                    levels=[{'n_out': r['n_out'], 'pairs': r['pairs'], 'launches': r['launches'], 'avg_launch_us': round(r['avg_us'], 2),
-                             'flops_per_launch': r['flops'], 'frac_of_fp32_mfma_peak': round(r['TFLOPs'] / MFMA_F32_PEAK_TFLOPS, 4),
-                             'compulsory_bytes_per_launch': r.get('compulsory_bytes'),
-                             'mfma_issued_flops_per_launch': r.get('mfma_issued_flops')} for r in sorted(d, key=lambda r: -r['n_out'])],
-                    algorithmic={'flops_per_launch': fl / launches, 'TFLOPs': round(tf, 2), 'frac_of_fp32_mfma_peak': round(mfma_frac, 4),
-                                 'compulsory_bytes_per_launch': comp / launches, 'compulsory_GBps': round(cg, 1), 'frac_of_hbm_peak': round(hbm_frac, 4),
-                                 'gathered_bytes_per_launch': gath / launches, 'gathered_GBps': round(gath / t_s / 1e9, 1),
-                                 'note': 'per-launch figures are means over the launches of this kernel name (levels pooled: see `levels`); gathered = SURVEY 8d '
-                                         'formula, every (in,out) pair charged — the row re-use is served by L2/LDS, not HBM'})
-        if issued:
-            roof['mfma_issued'] = {'flops_per_launch': issued / launches, 'TFLOPs': round(issued / t_s / 1e12, 2),
-                                   'pipe_utilisation': round(issued / t_s / 1e12 / MFMA_F32_PEAK_TFLOPS, 4), 'issued_over_algorithmic': round(issued / fl, 2),
-                                   'note': 'fp32 MFMA flops issued (zero-padded columns and absent rows included) / time'}
-        roof['all_launches'] = self.aggregate(peak_gbs, steps)
-        return roof
-
-    def aggregate(self, peak_gbs, steps):
-        d = [r for r in self.detail() if 'pairs' in r]
-        tot_g = sum(r['gathered_bytes'] * r['launches'] for r in d)
-        tot_c = sum(r.get('compulsory_bytes', 0) * r['launches'] for r in d)
-        tot_f = sum(r['flops'] * r['launches'] for r in d)
-        tot_ms = sum(r['ms'] for r in d)
-        return {'ms_per_step': round(tot_ms / steps, 3), 'launches_per_step': round(sum(r['launches'] for r in d) / steps, 2),
-                'GFLOP_per_step': round(tot_f / steps / 1e9, 2),
-                'TFLOPs': round(tot_f / (tot_ms * 1e-3) / 1e12, 2), 'frac_of_fp32_mfma_peak': round(tot_f / (tot_ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS, 4),
-                'compulsory_GBps': round(tot_c / (tot_ms * 1e-3) / 1e9, 1), 'frac_of_hbm_peak': round(tot_c / (tot_ms * 1e-3) / 1e9 / peak_gbs, 4),
-                'gathered_GBps': round(tot_g / (tot_ms * 1e-3) / 1e9, 1)}
-
-
-PROFILE = _Profile()
+# ------------------------------------------------------------------------------------------------ profiling hook (pcgcv2_amd/roofline.py)
+PROFILE = roofline._Profile()
 
 
 # ------------------------------------------------------------------------------------------------ dispatch policy (pcgcv2_amd/pathconfig.py)
@@ -357,7 +174,6 @@ def down_level(fine, stride_fine):
     count back in the middle (the one host synchronisation of a level) and finishes into upper-bound buffers
     -> (coarse int32 [n_coarse,4], parent_of int32 [n], down int32 [8,n_coarse]); coarse and down are views of buffers
     sized for n rows.  Canonical order: coarse rows in first-occurrence order of the quantised fine rows."""
-    import ctypes
     fine = _i32(fine)
     n, dev = fine.shape[0], fine.device
     cap = int(lib().pcgc_hash_capacity(n))
@@ -386,7 +202,6 @@ def pyramid(fine, stride_fine, levels):
     """`levels` strided levels below `fine` in one library call with ONE host synchronisation (pcgc_pyramid): every level is
     deduplicated straight from the input rows.  -> [(coarse, parent_of, down)] per level, the same tensors `levels` nested
     down_level() calls return (views of upper-bound buffers)."""
-    import ctypes
     fine = _i32(fine)
     n, dev = fine.shape[0], fine.device
     nbytes = int(lib().pcgc_pyramid_scratch_bytes(n, levels))
@@ -523,24 +338,13 @@ def conv_gather(nbr, x, W, bias, out=None, residual=None, relu=False, n_out=None
     if out is None:
         out = torch.empty((n_out, Cout), dtype=torch.float32, device=x.device)
     res_p, res_ld = (None, 0) if residual is None else (_p(_f32(residual)), _ld(residual))
-    prof = K == 27 and PROFILE.want(('conv', Cin, Cout, n_out))
-    if prof:
-        mfma = Cin in (16, 32, 64) and Cout in (16, 32, 64) and n_out >= 8192
-        e0, e1 = PROFILE.bracket(('conv', Cin, Cout, n_out), f'k3 gather conv Cin={Cin} Cout={Cout} (k_conv_gather_mfma*/dma, per-row gather)', n_out,
-                                 lambda P, a=Cin, b=Cout, n=n_out: P * a * 4 + P * 8 + n * b * 4,
-                                 lambda P, a=Cin, b=Cout: 2 * P * a * b,
-                                 compulsory=x.shape[0] * Cin * 4 + 27 * n_out * 4 + n_out * Cout * 4,
-                                 mfma_issued=(2 * 27 * ((n_out + 15) // 16 * 16) * Cin * Cout) if mfma else None)
-        e0.record()
-    check(lib().pcgc_conv_gather(_p(nbr), K, n_out, _p(x), x.shape[0], Cin, _ld(x), 0, _p(W), _p(bias), res_p, res_ld, 0, int(relu),
-                                 _p(out), Cout, _ld(out), 0, _stream(nbr)), 'conv_gather')
-    if prof:
-        e1.record()
-    elif PROFILE.counting and K == 27:
-        PROFILE.count(nbr)
+    key = ('conv', Cin, Cout, n_out)
+    wanted = K == 27 and PROFILE.want(key) and (key, roofline.k3_conv(
+        f'k3 gather conv Cin={Cin} Cout={Cout} (k_conv_gather_mfma*/dma, per-row gather)', Cin, Cout, n_out, n_in=x.shape[0],
+        issued=roofline.dense_issued(27, n_out, Cin, Cout) if Cin in (16, 32, 64) and Cout in (16, 32, 64) and n_out >= 8192 else None))
+    check(PROFILE.launch(wanted, nbr if K == 27 else None, None, lib().pcgc_conv_gather, _p(nbr), K, n_out, _p(x), x.shape[0], Cin, _ld(x), 0, _p(W),
+                         _p(bias), res_p, res_ld, 0, int(relu), _p(out), Cout, _ld(out), 0, _stream(nbr)), 'conv_gather')
     return out
-
-
 
 
 def conv_gather_unit(nbr, W, bias, relu=False):
@@ -553,17 +357,10 @@ def conv_gather_unit(nbr, W, bias, relu=False):
     n_out = nbr.shape[1]
     out = torch.empty((n_out, Cout), dtype=torch.float32, device=W.device)
     key = ('conv', 1, Cout, n_out)
-    prof = K == 27 and PROFILE.want(key)
-    if prof:
-        e0, e1 = PROFILE.bracket(key, f'k3 conv 1->{Cout} on the unit input (k_conv_unit: kernel map only, no feature gather)', n_out,
-                                 lambda P, b=Cout, n=n_out: P * 4 + P * 8 + n * b * 4, lambda P, b=Cout: 2 * P * b,
-                                 compulsory=27 * n_out * 4 + n_out * Cout * 4)
-        e0.record()
-    check(lib().pcgc_conv_gather_unit(_p(nbr), K, n_out, _p(W), _p(bias), int(relu), _p(out), Cout, Cout, _stream(nbr)), 'conv_gather_unit')
-    if prof:
-        e1.record()
-    elif PROFILE.counting and K == 27:
-        PROFILE.count(nbr)
+    wanted = K == 27 and PROFILE.want(key) and (key, roofline.unit_conv(
+        f'k3 conv 1->{Cout} on the unit input (k_conv_unit: kernel map only, no feature gather)', Cout, n_out))
+    check(PROFILE.launch(wanted, nbr if K == 27 else None, None, lib().pcgc_conv_gather_unit, _p(nbr), K, n_out, _p(W), _p(bias), int(relu), _p(out),
+                         Cout, Cout, _stream(nbr)), 'conv_gather_unit')
     return out
 
 
@@ -577,16 +374,10 @@ def conv_unit_from_coarse(fine, stride_fine, parent_of, coarse_nbr, down, W, bia
     n = fine.shape[0]
     out = torch.empty((n, Cout), dtype=torch.float32, device=W.device)
     key = ('conv', 1, Cout, n)
-    prof = PROFILE.want(key)
-    if prof:
-        e0, e1 = PROFILE.bracket(key, f'k3 conv 1->{Cout} on the unit input (k_conv_unit_coarse: presence from the parent level\'s map, no map of its own)', n,
-                                 lambda P, b=Cout, n=n: P * 4 + P * 8 + n * b * 4, lambda P, b=Cout: 2 * P * b,
-                                 compulsory=n * 16 + n * 4 + n * Cout * 4)
-        e0.record()
-    check(lib().pcgc_conv_unit_from_coarse(_p(_i32(fine)), n, int(stride_fine), _p(parent_of), _p(coarse_nbr), _p(down), coarse_nbr.shape[1],
-                                           _p(W), _p(bias), int(relu), _p(out), Cout, Cout, _stream(fine)), 'conv_unit_from_coarse')
-    if prof:
-        e1.record()
+    wanted = PROFILE.want(key) and (key, roofline.unit_conv(
+        f'k3 conv 1->{Cout} on the unit input (k_conv_unit_coarse: presence from the parent level\'s map, no map of its own)', Cout, n, mapless=True))
+    check(PROFILE.launch(wanted, None, None, lib().pcgc_conv_unit_from_coarse, _p(_i32(fine)), n, int(stride_fine), _p(parent_of), _p(coarse_nbr),
+                         _p(down), coarse_nbr.shape[1], _p(W), _p(bias), int(relu), _p(out), Cout, Cout, _stream(fine)), 'conv_unit_from_coarse')
     return out
 
 
@@ -595,21 +386,8 @@ def set_up2_impl(mfma):
     check(lib().pcgc_set_up2_impl(int(mfma)), 'set_up2_impl')
 
 
-
-
-def _irn_pass_formulas(n, C, map_bytes, names):
-    """[(pass, name, gathered_bytes(P), flops(P), compulsory_bytes)] of the two fused InceptionResNet passes on n rows."""
-    Q = C // 4
-    return ((1, names[0], lambda P: (P * C * 4 + P * 8 + n * Q * 4) + n * (C + Q) * 4, lambda P: 2 * P * C * Q + 2 * n * C * Q,
-             n * C * 4 + map_bytes + n * 2 * Q * 4),
-            (2, names[1], lambda P: (P * Q * 4 + P * 8 + n * 2 * Q * 4) + (P * Q * 4 + P * 8 + n * Q * 4) + n * 3 * Q * 4,
-             lambda P: 2 * P * Q * 2 * Q + 2 * P * Q * Q + 2 * n * Q * 2 * Q,
-             n * 2 * Q * 4 + map_bytes + n * C * 4 + n * C * 4))
-
-
 def irn_block(nbr, x, params):
     """Fused InceptionResNet block; params = [conv0_0.kernel, .bias, conv0_1.kernel, .bias, conv1_0..., conv1_1..., conv1_2...]."""
-    import ctypes
     _f32(x, 'x')
     n, C = x.shape
     t = torch.empty((n, C // 2), dtype=torch.float32, device=x.device)
@@ -617,52 +395,70 @@ def irn_block(nbr, x, params):
     arr = (ctypes.c_void_p * 10)(*[p.data_ptr() for p in params])
     if PROFILE.counting:
         PROFILE.count(nbr)
-    name_a, name_b = (f'k_irn_a<{C}, 16>', f'k_irn_b<{C}, 16>') if C == 64 else (f'k_irn_a_split<{C}>', f'k_irn_b_split<{C}>')
-    if not (PROFILE.want((name_a, n)) or PROFILE.want((name_b, n))):
+    names = (f'k_irn_a<{C}, 16>', f'k_irn_b<{C}, 16>') if C == 64 else (f'k_irn_a_split<{C}>', f'k_irn_b_split<{C}>')
+    if not (PROFILE.want((names[0], n)) or PROFILE.want((names[1], n))):
         check(lib().pcgc_irn_block(_p(nbr), n, _p(x), C, _ld(x), arr, _p(t), _p(out), C, _stream(nbr)), 'irn_block')
         return out
-    Q = C // 4
-    passes = _irn_pass_formulas(n, C, 27 * n * 4, (name_a, name_b))
-    for ps, name, bf, ff, comp in passes:
-        prof = PROFILE.want((name, n))
-        if prof:
-            e0, e1 = PROFILE.bracket((name, n), name + ' (per-row gather, VALU)', n, bf, ff, compulsory=comp)
-            e0.record()
-        check(lib().pcgc_irn_pass(_p(nbr), n, _p(x), C, _ld(x), arr, _p(t), _p(out), C, ps, _stream(nbr)), 'irn_pass')
-        if prof:
-            e1.record()
+    for ps in (1, 2):
+        key = (names[ps - 1], n)
+        wanted = PROFILE.want(key) and (key, roofline.irn_pass(ps, key[0] + ' (per-row gather, VALU)', n, C, n))
+        check(PROFILE.launch(wanted, None, None, lib().pcgc_irn_pass, _p(nbr), n, _p(x), C, _ld(x), arr, _p(t), _p(out), C, ps, _stream(nbr)), 'irn_pass')
     return out
 
 
+# The MFMA forms of the block share one native signature (include/pcgc_hip.h: pcgc_irn_rows_pass, _rows_q4_pass, _child_pass, _child_q4) and
+# differ in data only.  per_tile: MFMA instructions of pass A and pass B (its conv1_2 products included) per tile of `tile_rows` rows of the
+# map the kernel walks — the level's own, or (parent_map) its parents' [27][n / 8] map; mfma_flops: flops of one such instruction.
+_IrnVariant = namedtuple('_IrnVariant', 'entry label names desc per_tile tile_rows mfma_flops parent_map')
+_ROWS, _CHILD = ' (fused InceptionResNet pass on a plain level, ', ' (fused InceptionResNet pass on a children level, packed-N fp32 MFMA)'
+_IRN = {
+    'rows64': _IrnVariant('pcgc_irn_rows_pass', 'irn_rows_pass', ('k_rows_irn_a64', 'k_rows_irn_b64'),
+                          _ROWS + 'LDS-resident table + per-wave row ring, fp32 MFMA)', (27 * 16 + 16, 27 * 12 + 8), 16, 2048, False),
+    # (pass A: 8 K-steps per offset; pass B: 2 + 2, + conv1_2)
+    'rows32': _IrnVariant('pcgc_irn_rows_pass', 'irn_rows_pass', ('k_rows_irn_a32', 'k_rows_irn_b32'),
+                          _ROWS + 'LDS-resident table + per-wave row ring, packed-N fp32 MFMA)', (27 * 8, 27 * 4 + 2), 16, 2048, False),
+    # (4x4x1 instructions per 64-row M tile)
+    'rows32_q4': _IrnVariant('pcgc_irn_rows_q4_pass', 'irn_rows_q4_pass', ('k_rows_q4_a32', 'k_rows_q4_b32'),
+                             _ROWS + 'quad-block 4x4x1 fp32 MFMA, lane = row)', (112 * 16, 81 * 16 + 32), 64, 512, False),
+    'child<16>': _IrnVariant('pcgc_irn_child_pass', 'irn_child_pass', ('k_child_irn_a<16>', 'k_child_irn_b<16>'), _CHILD, (416, 248), 16, 2048, True),
+    'child<32>': _IrnVariant('pcgc_irn_child_pass', 'irn_child_pass', ('k_child_irn_a<32>', 'k_child_irn_b<32>'), _CHILD, (1216, 736), 16, 2048, True),
+    # pass A in quad-block form writes t in its T2 layout; pass B is the packed-N kernel with T2 gather addresses (csrc/child_q4.hip).  Pass A per
+    # 16 parents, in units of 2048 flops: 224 groups x 16 4x4x1 instructions (512 flops each) per 64 parents + the 128 transposing ones per 128
+    'child_q4': _IrnVariant('pcgc_irn_child_q4', 'irn_child_pass', ('k_child_q4<0, 8, 2>', 'k_child_irn_b<16>'), _CHILD,
+                            ((216 + 8) * 16 // 4 // 4 + 128 // 8 // 4, 248), 16, 2048, True),
+}
+
+
+def _irn_passes(v, nbr, x, params, ta, tb, passes=(1, 2), t=None):
+    """Pass A (x -> t [n, C/2], table ta) and pass B (t, x -> out [n, C], table tb) of the fused block in the form `v` of _IRN, through
+    the map `nbr` -> out; asked for pass A alone -> t."""
+    _f32(x, 'x')
+    n, C = x.shape
+    m = nbr.shape[1]
+    if 1 in passes:
+        t = torch.empty((n, C // 2), dtype=torch.float32, device=x.device)
+    out = torch.empty((n, C), dtype=torch.float32, device=x.device) if 2 in passes else None
+    P = [p.data_ptr() for p in params]
+    s = _stream(x)
+    entry = getattr(lib(), v.entry)
+    if PROFILE.counting:
+        (PROFILE.count_children if v.parent_map else PROFILE.count)(nbr)
+    for ps in passes:
+        key = (v.names[ps - 1], n)
+        wanted = PROFILE.want(key) and (key, roofline.irn_pass(ps, key[0] + v.desc, n, C, m,
+                                                               (m + v.tile_rows - 1) // v.tile_rows * v.per_tile[ps - 1] * v.mfma_flops))
+        if ps == 1:
+            rc = PROFILE.launch(wanted, None, None, entry, _p(nbr), m, C, 1, _p(x), _ld(x), _p(ta), ta.numel() * 4, P[1], P[5], None, None, 0, _p(t), C // 2, s)
+        else:
+            rc = PROFILE.launch(wanted, None, None, entry, _p(nbr), m, C, 2, _p(t), C // 2, _p(tb), tb.numel() * 4, P[3], P[7], P[9], _p(x), _ld(x), _p(out), C, s)
+        check(rc, v.label)
+    return t if out is None else out
 
 
 def irn_block_rows64(nbr, x, params, tables):
     """C = 64 InceptionResNet on a plain level through its own k3 map (k_rows_irn_a64, k_rows_irn_b64; tables = child_irn_tables(params));
     bit-identical to irn_block."""
-    _f32(x, 'x')
-    n = x.shape[0]
-    ta, tb = tables
-    t = torch.empty((n, 32), dtype=torch.float32, device=x.device)
-    out = torch.empty((n, 64), dtype=torch.float32, device=x.device)
-    P = [p.data_ptr() for p in params]
-    s = _stream(x)
-    if PROFILE.counting:
-        PROFILE.count(nbr)
-    tiles = (n + 15) // 16
-    forms = _irn_pass_formulas(n, 64, 27 * n * 4, ('k_rows_irn_a64', 'k_rows_irn_b64'))
-    per_tile = (27 * 16 + 16, 27 * 12 + 8)                   # MFMA instructions per 16-row tile (pass B incl. the conv1_2 products)
-    calls = (lambda: lib().pcgc_irn_rows_pass(_p(nbr), n, 64, 1, _p(x), _ld(x), _p(ta), ta.numel() * 4, P[1], P[5], None, None, 0, _p(t), 32, s),
-             lambda: lib().pcgc_irn_rows_pass(_p(nbr), n, 64, 2, _p(t), 32, _p(tb), tb.numel() * 4, P[3], P[7], P[9], _p(x), _ld(x), _p(out), 64, s))
-    for (ps, name, bf, ff, comp), call, mf in zip(forms, calls, per_tile):
-        prof = PROFILE.want((name, n))
-        if prof:
-            e0, e1 = PROFILE.bracket((name, n), name + ' (fused InceptionResNet pass on a plain level, LDS-resident table + per-wave row ring, fp32 MFMA)', n, bf, ff,
-                                     compulsory=comp, mfma_issued=tiles * mf * 2048)
-            e0.record()
-        check(call(), 'irn_rows_pass')
-        if prof:
-            e1.record()
-    return out
+    return _irn_passes(_IRN['rows64'], nbr, x, params, *tables)
 
 
 def _rows_irn32_index():
@@ -693,49 +489,14 @@ def rows_irn32_tables(params):
     return _gather_table(ia, flat), _gather_table(ib, flat)
 
 
-
-
 def irn_block_rows32(nbr, x, params, tables):
     """C = 32 InceptionResNet on a plain level through its own k3 map (k_rows_irn_a32 / _b32); bit-identical to irn_block."""
-    _f32(x, 'x')
-    n = x.shape[0]
-    ta, tb = tables
-    t = torch.empty((n, 16), dtype=torch.float32, device=x.device)
-    out = torch.empty((n, 32), dtype=torch.float32, device=x.device)
-    P = [p.data_ptr() for p in params]
-    s = _stream(x)
-    if PROFILE.counting:
-        PROFILE.count(nbr)
-    tiles = (n + 15) // 16
-    forms = _irn_pass_formulas(n, 32, 27 * n * 4, ('k_rows_irn_a32', 'k_rows_irn_b32'))
-    per_tile = (27 * 8, 27 * 4 + 2)                          # MFMA instructions per 16-row tile (pass A: 8 K-steps per offset; pass B: 2 + 2, + conv1_2)
-    calls = (lambda: lib().pcgc_irn_rows_pass(_p(nbr), n, 32, 1, _p(x), _ld(x), _p(ta), ta.numel() * 4, P[1], P[5], None, None, 0, _p(t), 16, s),
-             lambda: lib().pcgc_irn_rows_pass(_p(nbr), n, 32, 2, _p(t), 16, _p(tb), tb.numel() * 4, P[3], P[7], P[9], _p(x), _ld(x), _p(out), 32, s))
-    for (ps, name, bf, ff, comp), call, mf in zip(forms, calls, per_tile):
-        prof = PROFILE.want((name, n))
-        if prof:
-            e0, e1 = PROFILE.bracket((name, n), name + ' (fused InceptionResNet pass on a plain level, LDS-resident table + per-wave row ring, packed-N fp32 MFMA)', n, bf, ff,
-                                     compulsory=comp, mfma_issued=tiles * mf * 2048)
-            e0.record()
-        check(call(), 'irn_rows_pass')
-        if prof:
-            e1.record()
-    return out
+    return _irn_passes(_IRN['rows32'], nbr, x, params, *tables)
 
 
 def rows32_pass(nbr, x, params, tables, ps, t=None):
     """one pass of irn_block_rows32 on its own (A/B tools): ps = 1 -> t [n, 16]; ps = 2 (t given) -> out [n, 32]"""
-    n = x.shape[0]
-    ta, tb = tables
-    P = [p.data_ptr() for p in params]
-    s = _stream(x)
-    if ps == 1:
-        t = torch.empty((n, 16), dtype=torch.float32, device=x.device)
-        check(lib().pcgc_irn_rows_pass(_p(nbr), n, 32, 1, _p(x), _ld(x), _p(ta), ta.numel() * 4, P[1], P[5], None, None, 0, _p(t), 16, s), 'irn_rows_pass')
-        return t
-    out = torch.empty((n, 32), dtype=torch.float32, device=x.device)
-    check(lib().pcgc_irn_rows_pass(_p(nbr), n, 32, 2, _p(t), 16, _p(tb), tb.numel() * 4, P[3], P[7], P[9], _p(x), _ld(x), _p(out), 32, s), 'irn_rows_pass')
-    return out
+    return _irn_passes(_IRN['rows32'], nbr, x, params, *tables, passes=(ps,), t=t)
 
 
 def rows_q4_tables(params):
@@ -756,49 +517,14 @@ def rows_q4_tables(params):
     return torch.cat([a0, a1]).contiguous(), torch.cat([torch.cat([x01, y11], 1).reshape(-1), w12]).contiguous()
 
 
-
-
 def rows_q4_pass(nbr, x, params, tables, ps, t=None):
     """one pass of irn_block_rows32_q4 on its own (A/B tools)"""
-    n = x.shape[0]
-    ta, tb = tables
-    P = [p.data_ptr() for p in params]
-    s = _stream(x)
-    if ps == 1:
-        t = torch.empty((n, 16), dtype=torch.float32, device=x.device)
-        check(lib().pcgc_irn_rows_q4_pass(_p(nbr), n, 32, 1, _p(x), _ld(x), _p(ta), ta.numel() * 4, P[1], P[5], None, None, 0, _p(t), 16, s), 'irn_rows_q4_pass')
-        return t
-    out = torch.empty((n, 32), dtype=torch.float32, device=x.device)
-    check(lib().pcgc_irn_rows_q4_pass(_p(nbr), n, 32, 2, _p(t), 16, _p(tb), tb.numel() * 4, P[3], P[7], P[9], _p(x), _ld(x), _p(out), 32, s), 'irn_rows_q4_pass')
-    return out
+    return _irn_passes(_IRN['rows32_q4'], nbr, x, params, *tables, passes=(ps,), t=t)
 
 
 def irn_block_rows32_q4(nbr, x, params, tables):
     """C = 32 InceptionResNet on a plain level through its own k3 map, quad-block form (k_rows_q4_a32 / _b32); bit-identical to irn_block."""
-    _f32(x, 'x')
-    n = x.shape[0]
-    ta, tb = tables
-    t = torch.empty((n, 16), dtype=torch.float32, device=x.device)
-    out = torch.empty((n, 32), dtype=torch.float32, device=x.device)
-    P = [p.data_ptr() for p in params]
-    s = _stream(x)
-    if PROFILE.counting:
-        PROFILE.count(nbr)
-    tiles = (n + 63) // 64
-    forms = _irn_pass_formulas(n, 32, 27 * n * 4, ('k_rows_q4_a32', 'k_rows_q4_b32'))
-    per_tile = (112 * 16, 81 * 16 + 32)                      # 4x4x1 instructions (512 flops each) per 64-row M tile
-    calls = (lambda: lib().pcgc_irn_rows_q4_pass(_p(nbr), n, 32, 1, _p(x), _ld(x), _p(ta), ta.numel() * 4, P[1], P[5], None, None, 0, _p(t), 16, s),
-             lambda: lib().pcgc_irn_rows_q4_pass(_p(nbr), n, 32, 2, _p(t), 16, _p(tb), tb.numel() * 4, P[3], P[7], P[9], _p(x), _ld(x), _p(out), 32, s))
-    for (ps, name, bf, ff, comp), call, mf in zip(forms, calls, per_tile):
-        prof = PROFILE.want((name, n))
-        if prof:
-            e0, e1 = PROFILE.bracket((name, n), name + ' (fused InceptionResNet pass on a plain level, quad-block 4x4x1 fp32 MFMA, lane = row)', n, bf, ff,
-                                     compulsory=comp, mfma_issued=tiles * mf * 512)
-            e0.record()
-        check(call(), 'irn_rows_q4_pass')
-        if prof:
-            e1.record()
-    return out
+    return _irn_passes(_IRN['rows32_q4'], nbr, x, params, *tables)
 
 
 def set_rows_q4_variant(v):
@@ -806,30 +532,6 @@ def set_rows_q4_variant(v):
 
 
 # ------------------------------------------------------------------------------------------------ children-level convs
-
-
-def _halo_cells():
-    """The 64 cells of a parent's 4x4x4 halo in ascending (cz, cy, cx) order -> list of (kp, j', reach) where kp = index of the
-    neighbour parent in the PARENT level's k3 map, j' = which of its children the cell is, and reach = [(j, k)]: the children j
-    of the centre parent whose 3x3x3 window contains the cell, with the kernel offset k they see it through."""
-    P1 = (0, 1, 1, 2)                  # floor(c / 2) + 1 for c = -1, 0, 1, 2
-    B = (1, 0, 1, 0)                   # c & 1
-    cells = []
-    for cz in range(4):
-        for cy in range(4):
-            for cx in range(4):
-                kp = P1[cz] * 9 + P1[cy] * 3 + P1[cx]
-                jc = B[cx] + 2 * B[cy] + 4 * B[cz]
-                reach = []
-                for j in range(8):
-                    kx, ky, kz = cx - (j & 1), cy - ((j >> 1) & 1), cz - (j >> 2)          # = (c - j) + 1 per axis
-                    if 0 <= kx <= 2 and 0 <= ky <= 2 and 0 <= kz <= 2:
-                        reach.append((j, kz * 9 + ky * 3 + kx))
-                cells.append((kp, jc, reach))
-    assert sum(len(r) for _, _, r in cells) == 216
-    return cells
-
-
 def child_conv_table(W):
     """B-fragment table of pcgc_conv_child for a plain k3 conv `kernel` [27, Cin, Cout]:
     table[k][n][cb][lane][jj] = W[k][16 cb + 4 jj + (lane >> 4)][16 n + (lane & 15)]   (one lane-linear 1 KB fragment per
@@ -945,17 +647,11 @@ def cls_child_q4(parent_nbr, x, table, bias):
     n = 8 * n_p
     out = torch.empty((n, 1), dtype=torch.float32, device=x.device)
     key = ('child_conv', Cin, 1, n)
-    prof = PROFILE.want(key)
-    if prof:
-        e0, e1 = PROFILE.bracket(key, f'k_child_q4<1, 8, 2> (k3 {Cin}->1 on a children level, parent-map halo gather + quad-block 4x4x1 fp32 MFMA)', n,
-                                 lambda P, a=Cin: P * a * 4 + P * 8 + n * 4, lambda P, a=Cin: 2 * P * a,
-                                 compulsory=n * Cin * 4 + 27 * n_p * 4 + n * 4, mfma_issued=((n_p + 63) // 64) * 96 * 16 * 512)
-        e0.record()
-    check(lib().pcgc_cls_child_q4(_p(parent_nbr), n_p, _p(x), Cin, _ld(x), _p(table), table.numel() * 4, _p(bias), _p(out), _stream(x)), 'cls_child_q4')
-    if prof:
-        e1.record()
-    elif PROFILE.counting:
-        PROFILE.count_children(parent_nbr)
+    wanted = PROFILE.want(key) and (key, roofline.child_conv(
+        f'k_child_q4<1, 8, 2> (k3 {Cin}->1 on a children level, parent-map halo gather + quad-block 4x4x1 fp32 MFMA)', Cin, 1, n_p,
+        issued=((n_p + 63) // 64) * 96 * 16 * 512))
+    check(PROFILE.launch(wanted, None, parent_nbr, lib().pcgc_cls_child_q4, _p(parent_nbr), n_p, _p(x), Cin, _ld(x), _p(table), table.numel() * 4,
+                         _p(bias), _p(out), _stream(x)), 'cls_child_q4')
     return out
 
 
@@ -1060,8 +756,6 @@ def child_irn_tables(params):
     return _gather_table(ia, flat), (None if ib is None else _gather_table(ib, flat))
 
 
-
-
 def child_q4_tables(params):
     """Table of the quad-block pass A (pcgc_irn_child_q4, C = 16): [27][co 4][ci 16] = conv0_0.kernel[k][ci][co], then [co 4][ci 16] =
     conv1_0.kernel[0][ci][co] — a lane's operands of one (cell, child) pair are its output channel's 16 input channels, contiguous."""
@@ -1071,51 +765,15 @@ def child_q4_tables(params):
                       W10.detach().reshape(C, C // 4).t().reshape(-1)]).contiguous()
 
 
-
-
 def irn_block_child(parent_nbr, x, params, tables, q4_table=None):
     """Fused InceptionResNet on a children level through the parent map (C = 16, 32); bit-identical to irn_block."""
     _f32(x, 'x')
-    n_p = parent_nbr.shape[1]
     n, C = x.shape
-    if n != 8 * n_p:
+    if n != 8 * parent_nbr.shape[1]:
         raise PcgcError('irn_block_child: feature rows must be 8 x the parent level')
-    ta, tb = tables
-    t = torch.empty((n, C // 2), dtype=torch.float32, device=x.device)
-    out = torch.empty((n, C), dtype=torch.float32, device=x.device)
-    P = [p.data_ptr() for p in params]
-    s = _stream(x)
-    if PROFILE.counting:
-        PROFILE.count_children(parent_nbr)
-    tiles = (n_p + 15) // 16
-    per_tile = {16: (416, 248), 32: (1216, 736)}[C]          # MFMA instructions per 16-parent tile (incl. the conv1_2 products of pass B)
-    names = (f'k_child_irn_a<{C}>', f'k_child_irn_b<{C}>')
-    q4 = PATH.CHILD_Q4 and C == 16 and q4_table is not None
-    if q4:
-        # per 16 parents, in units of 2048 flops: 224 groups x 16 4x4x1 instructions (512 flops each) per 64 parents + the 128 transposing ones per 128
-        per_tile = ((216 + 8) * 16 // 4 // 4 + 128 // 8 // 4, per_tile[1])
-        names = ('k_child_q4<0, 8, 2>', 'k_child_irn_b<16>')            # (pass B: the T2-gather instantiation of the packed-N kernel)
-    forms = _irn_pass_formulas(n, C, 27 * n_p * 4, names)
-    if q4:      # pass A in quad-block form writes t in its T2 layout; pass B is the packed-N kernel with T2 gather addresses (csrc/child_q4.hip)
-        calls = (lambda: lib().pcgc_irn_child_q4(_p(parent_nbr), n_p, C, 1, _p(x), _ld(x), _p(q4_table), q4_table.numel() * 4, P[1], P[5], None,
-                                                 None, 0, _p(t), C // 2, s),
-                 lambda: lib().pcgc_irn_child_q4(_p(parent_nbr), n_p, C, 2, _p(t), C // 2, _p(tb), tb.numel() * 4, P[3], P[7], P[9], _p(x), _ld(x),
-                                                 _p(out), C, s))
-    else:
-        calls = (lambda: lib().pcgc_irn_child_pass(_p(parent_nbr), n_p, C, 1, _p(x), _ld(x), _p(ta), ta.numel() * 4, P[1], P[5], None, None, 0,
-                                                   _p(t), C // 2, s),
-                 lambda: lib().pcgc_irn_child_pass(_p(parent_nbr), n_p, C, 2, _p(t), C // 2, _p(tb), tb.numel() * 4, P[3], P[7], P[9], _p(x), _ld(x),
-                                                   _p(out), C, s))
-    for (ps, name, bf, ff, comp), call, mf in zip(forms, calls, per_tile):
-        prof = PROFILE.want((name, n))
-        if prof:
-            e0, e1 = PROFILE.bracket((name, n), name + ' (fused InceptionResNet pass on a children level, packed-N fp32 MFMA)', n, bf, ff,
-                                     compulsory=comp, mfma_issued=tiles * mf * 2048)
-            e0.record()
-        check(call(), 'irn_child_pass')
-        if prof:
-            e1.record()
-    return out
+    if PATH.CHILD_Q4 and C == 16 and q4_table is not None:
+        return _irn_passes(_IRN['child_q4'], parent_nbr, x, params, q4_table, tables[1])
+    return _irn_passes(_IRN[f'child<{C}>'], parent_nbr, x, params, *tables)
 
 
 def conv_child(parent_nbr, x, table, bias, Cout, out=None, residual=None, relu=False):
@@ -1130,25 +788,14 @@ def conv_child(parent_nbr, x, table, bias, Cout, out=None, residual=None, relu=F
     res_p, res_ld = (None, 0) if residual is None else (_p(_f32(residual)), _ld(residual))
     n = 8 * n_p
     key = ('child_conv', Cin, Cout, n)
-    prof = PROFILE.want(key)
-    if prof:
-        tiles = (n_p + 15) // 16
-        per_tile = 64 * (Cin // 16) * 4 if Cout == 1 else 216 * (Cin // 16) * (Cout // 16) * 4        # MFMA instructions per 16-parent tile
-        name = f'k_child_cls<{Cin // 16}>' if Cout == 1 else f'k_child_conv<{Cin // 16}, {Cout // 16}>'
-        e0, e1 = PROFILE.bracket(key, name + f' (k3 {Cin}->{Cout} on a children level, parent-map halo gather + fp32 MFMA)', n,
-                                 lambda P, a=Cin, b=Cout: P * a * 4 + P * 8 + n * b * 4, lambda P, a=Cin, b=Cout: 2 * P * a * b,
-                                 compulsory=n * Cin * 4 + 27 * n_p * 4 + n * Cout * 4 + (0 if residual is None else n * Cout * 4),
-                                 mfma_issued=tiles * per_tile * 2048)
-        e0.record()
-    check(lib().pcgc_conv_child(_p(parent_nbr), n_p, _p(x), Cin, _ld(x), _p(table), table.numel() * 4, _p(bias), res_p, res_ld,
-                                int(relu), _p(out), Cout, _ld(out), _stream(x)), 'conv_child')
-    if prof:
-        e1.record()
-    elif PROFILE.counting:
-        PROFILE.count_children(parent_nbr)
+    # (MFMA instructions per 16-parent tile: 64 per 16-channel block and K-step for the head, 216 per block pair and K-step otherwise)
+    wanted = PROFILE.want(key) and (key, roofline.child_conv(
+        (f'k_child_cls<{Cin // 16}>' if Cout == 1 else f'k_child_conv<{Cin // 16}, {Cout // 16}>')
+        + f' (k3 {Cin}->{Cout} on a children level, parent-map halo gather + fp32 MFMA)', Cin, Cout, n_p, residual is not None,
+        (n_p + 15) // 16 * (64 * (Cin // 16) * 4 if Cout == 1 else 216 * (Cin // 16) * (Cout // 16) * 4) * 2048))
+    check(PROFILE.launch(wanted, None, parent_nbr, lib().pcgc_conv_child, _p(parent_nbr), n_p, _p(x), Cin, _ld(x), _p(table), table.numel() * 4,
+                         _p(bias), res_p, res_ld, int(relu), _p(out), Cout, _ld(out), _stream(x)), 'conv_child')
     return out
-
-
 
 
 def conv_rows(nbr, x, table, bias, Cout, out=None, residual=None, relu=False):
@@ -1159,22 +806,12 @@ def conv_rows(nbr, x, table, bias, Cout, out=None, residual=None, relu=False):
         out = torch.empty((n, Cout), dtype=torch.float32, device=x.device)
     res_p, res_ld = (None, 0) if residual is None else (_p(_f32(residual)), _ld(residual))
     key = ('conv', Cin, Cout, n)
-    prof = PROFILE.want(key)
-    if prof:
-        e0, e1 = PROFILE.bracket(key, f'k_rows_conv<{Cin // 16}, {Cout // 16}> (k3 {Cin}->{Cout} on a plain level, LDS-resident table + per-wave row ring, fp32 MFMA)', n,
-                                 lambda P, a=Cin, b=Cout: P * a * 4 + P * 8 + n * b * 4, lambda P, a=Cin, b=Cout: 2 * P * a * b,
-                                 compulsory=n * Cin * 4 + 27 * n * 4 + n * Cout * 4 + (0 if residual is None else n * Cout * 4),
-                                 mfma_issued=2 * 27 * ((n + 15) // 16 * 16) * Cin * Cout)
-        e0.record()
-    check(lib().pcgc_conv_rows(_p(nbr), n, _p(x), Cin, _ld(x), _p(table), table.numel() * 4, _p(bias), res_p, res_ld, int(relu), _p(out), Cout,
-                               _ld(out), _stream(x)), 'conv_rows')
-    if prof:
-        e1.record()
-    elif PROFILE.counting:
-        PROFILE.count(nbr)
+    wanted = PROFILE.want(key) and (key, roofline.k3_conv(
+        f'k_rows_conv<{Cin // 16}, {Cout // 16}> (k3 {Cin}->{Cout} on a plain level, LDS-resident table + per-wave row ring, fp32 MFMA)', Cin, Cout, n,
+        residual=residual is not None, issued=roofline.dense_issued(27, n, Cin, Cout)))
+    check(PROFILE.launch(wanted, nbr, None, lib().pcgc_conv_rows, _p(nbr), n, _p(x), Cin, _ld(x), _p(table), table.numel() * 4, _p(bias), res_p, res_ld,
+                         int(relu), _p(out), Cout, _ld(out), _stream(x)), 'conv_rows')
     return out
-
-
 
 
 def conv_packed64(nbr, x, table, bias, relu=False):
@@ -1183,23 +820,13 @@ def conv_packed64(nbr, x, table, bias, relu=False):
     n = x.shape[0]
     out = torch.empty((n, 64), dtype=torch.float32, device=x.device)
     key = ('conv', 64, 64, n)
-    prof = PROFILE.want(key)
-    if prof:
-        # MFMA flops issued: the present pairs in packed 16-row tiles, plus about half a tile of padding per (workgroup tile of ~96 rows, offset)
-        e0, e1 = PROFILE.bracket(key, 'k_conv_packed64 (k3 64->64, present-row packing: accumulators in LDS, B fragments in registers, fp32 MFMA)', n,
-                                 lambda P, n=n: P * 64 * 4 + P * 8 + n * 64 * 4, lambda P: 2 * P * 64 * 64,
-                                 compulsory=n * 64 * 4 + 27 * n * 4 + n * 64 * 4,
-                                 mfma_issued=lambda P, n=n: 2 * (P + 8 * 27 * ((n + 95) // 96)) * 64 * 64)
-        e0.record()
-    check(lib().pcgc_conv_packed64(_p(nbr), n, _p(x), _ld(x), _p(table), table.numel() * 4, _p(bias), int(relu), _p(out), 64, _stream(x)),
-          'conv_packed64')
-    if prof:
-        e1.record()
-    elif PROFILE.counting:
-        PROFILE.count(nbr)
+    # MFMA flops issued: the present pairs in packed 16-row tiles, plus about half a tile of padding per (workgroup tile of ~96 rows, offset)
+    wanted = PROFILE.want(key) and (key, roofline.k3_conv(
+        'k_conv_packed64 (k3 64->64, present-row packing: accumulators in LDS, B fragments in registers, fp32 MFMA)', 64, 64, n,
+        issued=lambda P: 2 * (P + 8 * 27 * ((n + 95) // 96)) * 64 * 64))
+    check(PROFILE.launch(wanted, nbr, None, lib().pcgc_conv_packed64, _p(nbr), n, _p(x), _ld(x), _p(table), table.numel() * 4, _p(bias), int(relu),
+                         _p(out), 64, _stream(x)), 'conv_packed64')
     return out
-
-
 
 
 def conv_down_rows(down, x, table, bias, Cout, relu=False):
@@ -1209,17 +836,10 @@ def conv_down_rows(down, x, table, bias, Cout, relu=False):
     n_c = down.shape[1]
     out = torch.empty((n_c, Cout), dtype=torch.float32, device=x.device)
     key = ('down', Cin, Cout, n_c)
-    prof = PROFILE.want(key)
-    if prof:      # k2 s2: every fine row is one (in,out) pair (bytes = N_fine Cin 4 + N_coarse Cout 4, flops = 2 N_fine Cin Cout)
-        e0, e1 = PROFILE.bracket(key, f'k_rows_down<{Cin // 16}, {Cout // 16}> (k2 s2 {Cin}->{Cout} through the down map, LDS-resident table, fp32 MFMA)', n_c,
-                                 lambda P, a=Cin, b=Cout: P * a * 4 + n_c * b * 4, lambda P, a=Cin, b=Cout: 2 * P * a * b,
-                                 compulsory=n_in * Cin * 4 + 8 * n_c * 4 + n_c * Cout * 4,
-                                 mfma_issued=2 * 8 * ((n_c + 15) // 16 * 16) * Cin * Cout, pairs=n_in)
-        e0.record()
-    check(lib().pcgc_conv_down_rows(_p(down), n_c, _p(x), n_in, Cin, _ld(x), _p(table), table.numel() * 4, _p(bias), int(relu), _p(out), Cout,
-                                    _ld(out), _stream(x)), 'conv_down_rows')
-    if prof:
-        e1.record()
+    wanted = PROFILE.want(key) and (key, roofline.down_conv(
+        f'k_rows_down<{Cin // 16}, {Cout // 16}> (k2 s2 {Cin}->{Cout} through the down map, LDS-resident table, fp32 MFMA)', Cin, Cout, n_c, n_in))
+    check(PROFILE.launch(wanted, None, None, lib().pcgc_conv_down_rows, _p(down), n_c, _p(x), n_in, Cin, _ld(x), _p(table), table.numel() * 4, _p(bias),
+                         int(relu), _p(out), Cout, _ld(out), _stream(x)), 'conv_down_rows')
     return out
 
 
@@ -1230,30 +850,29 @@ def conv_up2(x, W, bias, relu=False, rows=None):
     K, Cin, Cout = W.shape
     n_in = x.shape[0] if rows is None else rows.shape[0]
     key = ('up2', Cin, Cout, 8 * n_in)
-    prof = PROFILE.want(key)
-    if prof:      # generative transpose k2 s2: P = fine rows (bytes = N_fine (Cin + Cout) 4, flops = 2 N_fine Cin Cout)
-        mfma = (Cin, Cout) in ((64, 32), (32, 16))
-        e0, e1 = PROFILE.bracket(key, f'k_conv_up2<{Cin}, {Cout}> (generative transpose k2 s2, ' + ('eight GEMMs sharing the A fragments, fp32 MFMA)' if mfma else
-                                 'one thread per (row, 16-byte chunk), VALU)'), 8 * n_in,
-                                 lambda P, a=Cin, b=Cout: P * (a + b) * 4, lambda P, a=Cin, b=Cout: 2 * P * a * b,
-                                 compulsory=n_in * Cin * 4 + 8 * n_in * Cout * 4 + (0 if rows is None else n_in * 4),
-                                 mfma_issued=(2 * 8 * ((n_in + 15) // 16 * 16) * Cin * Cout) if mfma else None, pairs=8 * n_in)
-        e0.record()
-    try:
-        if rows is not None:
-            out = torch.empty((8 * rows.shape[0], Cout), dtype=torch.float32, device=x.device)
-            rc = lib().pcgc_conv_up2_gather(rows.shape[0], _p(x), Cin, _ld(x), _p(rows), _p(W), _p(bias), int(relu), _p(out), Cout, _stream(x))
-            if rc == 0:
-                return out
-            if rc != -3:
-                check(rc, 'conv_up2_gather')
-            x = gather_rows(x, rows)
-        out = torch.empty((8 * x.shape[0], Cout), dtype=torch.float32, device=x.device)
-        check(lib().pcgc_conv_up2(x.shape[0], _p(x), Cin, _ld(x), _p(W), _p(bias), int(relu), _p(out), Cout, _stream(x)), 'conv_up2')
-        return out
-    finally:
-        if prof:
-            e1.record()
+    wanted = PROFILE.want(key) and (key, _up2_work(Cin, Cout, n_in, rows is not None))
+    return PROFILE.launch(wanted, None, None, _conv_up2, x, W, bias, relu, rows)      # (the bracket closes on the early return too)
+
+
+def _up2_work(Cin, Cout, n_in, rows):
+    mfma = (Cin, Cout) in ((64, 32), (32, 16))
+    return roofline.up2_conv(f'k_conv_up2<{Cin}, {Cout}> (generative transpose k2 s2, ' + ('eight GEMMs sharing the A fragments, fp32 MFMA)' if mfma else
+                             'one thread per (row, 16-byte chunk), VALU)'), Cin, Cout, n_in, rows, mfma)
+
+
+def _conv_up2(x, W, bias, relu, rows):
+    Cin, Cout = W.shape[1:]
+    if rows is not None:
+        out = torch.empty((8 * rows.shape[0], Cout), dtype=torch.float32, device=x.device)
+        rc = lib().pcgc_conv_up2_gather(rows.shape[0], _p(x), Cin, _ld(x), _p(rows), _p(W), _p(bias), int(relu), _p(out), Cout, _stream(x))
+        if rc == 0:
+            return out
+        if rc != -3:
+            check(rc, 'conv_up2_gather')
+        x = gather_rows(x, rows)
+    out = torch.empty((8 * x.shape[0], Cout), dtype=torch.float32, device=x.device)
+    check(lib().pcgc_conv_up2(x.shape[0], _p(x), Cin, _ld(x), _p(W), _p(bias), int(relu), _p(out), Cout, _stream(x)), 'conv_up2')
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ select / sort
@@ -1292,7 +911,6 @@ def batch_counts(coords):
 
 
 def _i64_array(values):
-    import ctypes
     return (ctypes.c_int64 * len(values))(*[int(v) for v in values])
 
 
@@ -1308,8 +926,6 @@ def topk_mask_segments(logits, seg_rows, seg_k):
     check(lib().pcgc_topk_mask_segments(_p(logits), logits.stride(0), len(seg_rows), _i64_array(seg_rows), _i64_array(seg_k), _p(mask), _p(ws),
                                         ws_bytes, _stream(logits)), 'topk_mask_segments')
     return mask
-
-
 
 
 def topk_select(logits, seg_rows, seg_k, coords=None, parent_coords=None, parent_stride=0):
@@ -2274,14 +1890,12 @@ def rc_decode_ctx(cdf_u16, ctx, data):
 
 def _stems(stems):
     """file stems as a C array of byte strings (+ the Python objects that own the bytes)"""
-    import ctypes
     enc = [_os.fsencode(s) for s in stems]
     return (ctypes.c_char_p * len(enc))(*enc), enc
 
 
 def _table_fn():
     """address of pcgc_reference_table (libpcgc_reftable.so): the CDF table in the reference's arithmetic, callable from native threads"""
-    import ctypes
     from ._lib import reftable_lib
     return ctypes.cast(reftable_lib().pcgc_reference_table, ctypes.c_void_p)
 
@@ -2321,7 +1935,6 @@ def items_encode(stems, sym_h, xyz8, rows, ranges, counts, eb_params, index_segm
 
 def items_probe(stems):
     """-> (rows int64 [n], C, ranges float32 [n, 2], counts int32 [n, 3], native_coords int32 [n]) from the files of every item."""
-    import ctypes
     n = len(stems)
     arr, keep = _stems(stems)
     rows, ranges, counts, native = np.zeros(n, np.int64), np.zeros((n, 2), np.float32), np.zeros((n, 3), np.int32), np.zeros(n, np.int32)
@@ -2359,7 +1972,6 @@ def frame_decode(stem, C, eb_params, sym_buf, level_buf, use_sidecar=True, level
     """One cloud's files -> symbols and sorted coordinate level, in ONE library call, into the caller's (pinned) numpy buffers sym_buf
     int16 [cap, C] and level_buf int32 [cap, 4].  -> (rows, (min_v, max_v), (N4, N2, N1), native_coords), or (rows_needed, None, None,
     None) when the buffers are too small (nothing decoded: grow them and call again)."""
-    import ctypes
     cap = min(sym_buf.shape[0], level_buf.shape[0])
     if sym_buf.dtype != np.int16 or level_buf.dtype != np.int32 or sym_buf.shape[1:] != (C,) or level_buf.shape[1:] != (4,) \
             or not sym_buf.flags.c_contiguous or not level_buf.flags.c_contiguous:
@@ -2381,7 +1993,6 @@ def frame_decode_begin(stem, C, eb_params, sym_buf, level_buf, use_sidecar=True,
     """frame_decode in two halves: returns as soon as the coordinate level is in level_buf (the feature stream keeps decoding on the
     library's threads) -> the same tuple as frame_decode; the symbols in sym_buf are valid only after frame_decode_end().  When the
     buffers are too small (rows_needed, None, None, None) nothing is pending."""
-    import ctypes
     cap = min(sym_buf.shape[0], level_buf.shape[0])
     if sym_buf.dtype != np.int16 or level_buf.dtype != np.int32 or sym_buf.shape[1:] != (C,) or level_buf.shape[1:] != (4,) \
             or not sym_buf.flags.c_contiguous or not level_buf.flags.c_contiguous:
