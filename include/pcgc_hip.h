@@ -244,9 +244,19 @@ int pcgc_conv_down_rows(const int32_t* down, int64_t n_coarse, const float* in, 
  * output element as pcgc_conv_gather: bit-identical results. */
 int pcgc_conv_packed64(const int32_t* nbr, int64_t n, const float* in, int in_ld, const float* table, int64_t table_bytes,
                        const float* bias, int relu, float* out, int out_ld, void* stream);
-/* A/B switch of pcgc_conv_packed64: rows per workgroup tile (1 .. 128; 0 = chosen per launch from the level size); `waves` must be 0 or 4
- * (the eight-wave form was removed in round 5).  Results do not depend on it. */
+/* A/B switch of pcgc_conv_packed64: rows per workgroup tile (an even value in 40 .. 128 — the sizes the per-launch choice can take, each of
+ * them tested; 0 = chosen per launch from the level size); `waves` must be 0 or 4 (the eight-wave form was removed in round 5).  Anything
+ * else returns -1 and changes nothing.  Results do not depend on it. */
 int pcgc_set_packed_tuning(int rows, int waves);
+
+/* Tile schedules (csrc/tile_sched.h) under test.  pcgc_set_sched_cus: the compute-unit count every launcher sizes its grid by — 0 = the
+ * current device's own (the default), a positive value = that many (1: a persistent grid of 8 workgroups, so a few thousand rows reach a second
+ * round; 1 << 20: one tile per wave); negative: -1, nothing changes.  Process-wide; results never depend on it.
+ * pcgc_last_sched: out = (work units, workgroups, waves per workgroup) of this thread's most recent launch of a persistent tiled kernel
+ * (the children-level and rows kernels, the LDS-table form of pcgc_conv_up2), recorded where the grid is computed; after
+ * pcgc_conv_packed64: (tiles, workgroups, rows per workgroup R). */
+int pcgc_set_sched_cus(int cus);
+int pcgc_last_sched(int64_t out[3]);
 
 /* ‡ conventions the reference's results depend on but its sources do not pin (un-vendored MinkowskiEngine / torch.topk on ME's row
  * order): what = 0: top-k tie rule, value 0 = the lower row wins (default), 1 = the higher row wins.  The dedup policy is an argument of

@@ -59,6 +59,8 @@ SIGNATURES = {
     'pcgc_set_rows_q4_variant': (ci, [ci]),
     'pcgc_conv_packed64': (ci, [vp, i64, vp, ci, vp, i64, vp, ci, vp, ci, vp]),
     'pcgc_set_packed_tuning': (ci, [ci, ci]),
+    'pcgc_set_sched_cus': (ci, [ci]),
+    'pcgc_last_sched': (ci, [vp]),
     'pcgc_conv_up2': (ci, [i64, vp, ci, ci, vp, vp, ci, vp, ci, vp]),
     'pcgc_conv_up2_gather': (ci, [i64, vp, ci, ci, vp, vp, vp, ci, vp, ci, vp]),
     'pcgc_topk_workspace_bytes': (sz, [i64]),

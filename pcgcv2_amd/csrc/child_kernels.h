@@ -284,14 +284,8 @@ template <class V> constexpr int frag_floats() { return (V::HALF ? 32 : 64) * V:
 // instead of one-tile workgroups whose last round would run nearly empty; the table is staged once per workgroup.
 template <int NW, bool PERSIST = true>
 __device__ __forceinline__ int64_t child_tile(int i, int wave, int64_t ntiles) {
-    if constexpr (!PERSIST) {                                  // one tile per wave (levels with many more tiles than resident waves)
-        const int64_t tile = (int64_t)xcd_tile(blockIdx.x, gridDim.x) * NW + wave;
-        return (i == 0 && tile < ntiles) ? tile : -1;
-    }
-    const int64_t S = (ntiles + 7) >> 3;
-    const int64_t l = (blockIdx.x >> 3) + (int64_t)(gridDim.x >> 3) * (wave + NW * i);
-    const int64_t tile = (blockIdx.x & 7) * S + l;
-    return (l < S && tile < ntiles) ? tile : -1;
+    if constexpr (!PERSIST) return sched_child_tile_once(blockIdx.x, gridDim.x, NW, wave, i, ntiles);   // one tile per wave
+    return sched_child_tile(blockIdx.x, gridDim.x, NW, wave, i, ntiles);                                 // (tile_sched.h)
 }
 
 // Stage the B-fragment table into LDS (all waves), once per workgroup.
@@ -865,16 +859,9 @@ int child_lds_limit(K kern, size_t lds, ChildLdsGrant& granted) {
 // persistent grid: as many workgroups as stay resident (LDS-limited, at most 16 waves per CU), a multiple of 8 (one share per XCD).
 // n_units: work items of the launch (tiles of 16 MT parents, x 2 for half units)
 static unsigned child_grid_units(int64_t n_units, int nw, size_t lds, int max_waves_per_cu = 16) {
-    static int cus = 0;
-    if (!cus) { hipDeviceProp_t p; int dev = 0; (void)hipGetDevice(&dev); cus = (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256; }
-    int per_cu = (int)((160 * 1024) / (lds ? lds : 1));
-    if (per_cu > max_waves_per_cu / nw) per_cu = max_waves_per_cu / nw;
-    if (per_cu < 1) per_cu = 1;
-    int64_t want = (n_units + nw - 1) / nw;
-    int64_t g = (int64_t)cus * per_cu;
-    if (g > want) g = want;
-    g = (g + 7) / 8 * 8;
-    return (unsigned)g;
+    const unsigned g = sched_child_grid(n_units, nw, lds, pcgc_sched_cus(), max_waves_per_cu);         // (tile_sched.h)
+    pcgc_sched_record(n_units, g, nw);
+    return g;
 }
 static unsigned child_grid(int64_t n_p, int nw, size_t lds, int units_per_tile = 1) {
     return child_grid_units(((n_p + 15) / 16) * units_per_tile, nw, lds);

@@ -1136,6 +1136,7 @@ static int launch_up2_mfma(int64_t n_in, const float* in, int in_ld, const int32
                            hipStream_t s) {
     // 16 parent rows per wave: these levels are small (71 k / 256 k parents) and a wave runs its eight k serially, so more, shorter
     // waves win (measured us for 64->32 / 32->16: 16 rows 58 / 58, 32 rows 70 / 59, 64 rows 99 / 68; VALU form 97 / 123)
+    pcgc_sched_record((n_in + 15) >> 4, grid_for(n_in, 64), 4);                                       // (one 16-row tile per wave: never a second round)
     hipLaunchKernelGGL((k_conv_up2_mfma<CIN, COUT, 1>), dim3(grid_for(n_in, 64)), dim3(256), 0, s, n_in, in, in_ld, rows, W, bias, relu, out);
     return 0;
 }
@@ -1167,7 +1168,7 @@ k_conv_up2_tab(int64_t n_in, const float* __restrict__ in, int in_ld, const int3
 #pragma unroll
     for (int n = 0; n < NT; ++n) bv[n] = bias ? bias[16 * n + mi] : 0.0f;
     const int64_t ntiles = (n_in + 15) >> 4;
-    const int64_t tstep = (int64_t)gridDim.x * NW;
+    const int64_t tstep = sched_up2_step(gridDim.x, NW), tile0 = sched_up2_first(blockIdx.x, NW, wave);      // (tile_sched.h)
     // the tile's rows (lane (mi, mq): chunk mq of row mi of each 16-channel block), requested one tile ahead: a wave runs ~2 tiles and two waves
     // share a SIMD, so a load latency in front of every tile would be a fifth of its time
     auto fetch = [&](int64_t tile, float4 (&raw)[NB]) {
@@ -1178,8 +1179,8 @@ k_conv_up2_tab(int64_t n_in, const float* __restrict__ in, int in_ld, const int3
         for (int cb = 0; cb < NB; ++cb) raw[cb] = ok ? *(const float4*)(in + src * in_ld + 16 * cb + 4 * mq) : make_float4(0.f, 0.f, 0.f, 0.f);
     };
     float4 nxt[NB];
-    fetch((int64_t)blockIdx.x * NW + wave, nxt);
-    for (int64_t tile = (int64_t)blockIdx.x * NW + wave; tile < ntiles; tile += tstep) {
+    fetch(tile0, nxt);
+    for (int64_t tile = tile0; tile < ntiles; tile += tstep) {
         const int64_t p0 = tile * 16;
         float4 a[NB];
 #pragma unroll
@@ -1247,13 +1248,10 @@ static int launch_up2_tab(int64_t n_in, const float* in, int in_ld, const int32_
         if (e != hipSuccess) { pcgc_set_error("conv_up2: cannot raise the LDS limit to %zu: %s", lds, hipGetErrorString(e)); return -1; }
         granted[dev & 15] = true;
     }
-    static int cus = 0;
-    if (!cus) { hipDeviceProp_t p; cus = (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256; }
     const int64_t ntiles = (n_in + 15) >> 4;
-    const int per_cu = (int)((160 * 1024) / lds) > 2 ? 2 : ((160 * 1024) / lds < 1 ? 1 : (int)((160 * 1024) / lds));      // (16 waves per CU at most)
-    int64_t g = (ntiles + NW - 1) / NW;
-    if (g > (int64_t)cus * per_cu) g = (int64_t)cus * per_cu;
-    hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(NW * 64), lds, s, n_in, in, in_ld, rows, W, bias, relu, out);
+    const unsigned g = sched_up2_grid(ntiles, NW, lds, pcgc_sched_cus());                              // (tile_sched.h)
+    pcgc_sched_record(ntiles, g, NW);
+    hipLaunchKernelGGL(kern, dim3(g), dim3(NW * 64), lds, s, n_in, in, in_ld, rows, W, bias, relu, out);
     return 0;
 }
 static int g_up2_mfma = 2;          // 2 = LDS-resident fragment table (default), 1 = fragments from L2, 0 = VALU form (A/B tests)

@@ -18,15 +18,7 @@
 
 namespace {
 
-constexpr int PK_RMAX = 128;                    // output rows per workgroup: R <= 128 (two ballots), chosen per launch (pk_rows)
-constexpr int PK_ACC_LD = 68;                   // floats per accumulator row in LDS (64 + 4: rows start 4 banks apart)
-// LDS of a workgroup of R rows: accumulators (+ one dummy row for the padding slots of the last packed tile) | gathered rows of one offset
-// (up to ceil(R / 16) packed tiles x 4 KB) | per wave: gather row + output row of every packed slot
-__host__ __device__ constexpr int pk_tiles(int R) { return (R + 15) / 16; }
-__host__ __device__ constexpr int pk_acc_bytes(int R) { return (R + 1) * PK_ACC_LD * 4; }
-__host__ __device__ constexpr int pk_a_bytes(int R) { return pk_tiles(R) * 4096; }
-__host__ __device__ constexpr int pk_slots(int R) { return pk_tiles(R) * 16; }
-__host__ __device__ constexpr int pk_lds(int R, int NW) { return pk_acc_bytes(R) + pk_a_bytes(R) + NW * 2 * pk_slots(R) * 4; }
+// PK_RMAX, PK_ACC_LD, the LDS layout sizes pk_* and the choice of R (pk_rows): tile_sched.h
 
 // NW = 4 or 8 waves: wave w multiplies against column tile w & 3; with eight waves the packed tiles of an offset alternate between the two
 // waves of a column tile (group = w >> 2) — different rows inside an offset, and the barriers between offsets order the rest
@@ -183,47 +175,13 @@ k_conv_packed64(const int32_t* __restrict__ nbr, int64_t n, const float* __restr
     }
 }
 
-// Rows per workgroup, from a cost model fitted to sweeps of R on both layers of a vox10 frame (profiles/r04_conv_packed.md).  A launch is
-// `tiles` workgroups on cus x occ(R) slots (occ: LDS-limited workgroups per CU; LDS is granted in 1280-byte granules); a CU runs c workgroups
-// side by side, each offset costing about L + c W tau(c) us: L = what nobody covers (barriers, gather latency), W = R p / 16 + 1/2 packed tiles
-// per offset (the + 1/2 is the half-empty last tile), tau = time per packed tile, larger when few waves share a SIMD.  Large R packs better
-// but leaves two workgroups per CU; and e.g. 71 216 rows in tiles of 96 are 742 workgroups on 512 slots — two rounds — where tiles of 94
-// are 758 on 768: one.  p = 0.6 (a surface level has 14-19 of 27 neighbours; the choice is flat in p).
-int pk_occ(int R, int nw) {
-    const int granules = (pk_lds(R, nw) + 1279) / 1280;
-    int occ = (160 * 1024) / (granules * 1280);
-    const int by_waves = 24 / nw;                               // 84 VGPRs: six waves per SIMD
-    if (occ > by_waves) occ = by_waves;
-    return occ < 1 ? 1 : occ;
-}
-int pk_rows(int64_t n, int cus) {
-    auto tau = [](int c) { return c >= 4 ? 0.219 : (c == 3 ? 0.240 : (c == 2 ? 0.276 : 0.370)); };      // (least-squares fit to the two sweeps: 4 % rms)
-    auto cost_of = [&](int R) {
-        const int occ = pk_occ(R, 4);
-        const int64_t tiles = (n + R - 1) / R, slots = (int64_t)cus * occ;
-        const double W = R * 0.6 / 16.0 + 0.346, L = 1.27;
-        const int64_t full = tiles / slots, rem = tiles - full * slots;
-        double cost = (double)full * (L + occ * W * tau(occ));
-        if (rem) { const int c = (int)((rem + cus - 1) / cus); cost += L + c * W * tau(c); }
-        return cost;
-    };
-    double best_cost = 1e300;
-    int best = PK_RMAX;
-    for (int R = PK_RMAX; R >= 40; R -= 2)
-        if (cost_of(R) < best_cost) { best_cost = cost_of(R); best = R; }
-    // The model is flat to within its own error (4 % rms) over wide ranges of R — 149 856 rows: 260.5 at R = 50, 264.4 at 60, where the
-    // measured sweep has 298 and 288 us (profiles/r04_conv_packed.md) — so among the sizes within 2 % of its minimum the LARGEST is taken
-    // larger tiles pack better than the model's fixed + 1/2 tile per offset credits them with (round 5: conv0 picks 60 instead of 50).
-    // (only among tiles of the minimum's own occupancy: across an occupancy step the model's error is not a few per cent)
-    for (int R = PK_RMAX; R >= 40; R -= 2)
-        if (cost_of(R) <= 1.02 * best_cost && pk_occ(R, 4) == pk_occ(best, 4)) return R;
-    return best;
-}
 int g_pk_rows = 0;                                              // A/B: rows per workgroup forced (0 = default)
 
 }  // namespace
 extern "C" int pcgc_set_packed_tuning(int rows, int waves) {
-    if (rows < 0 || rows > PK_RMAX || (waves != 0 && waves != 4)) return -1;      // (four waves per workgroup: the eight-wave form lost everywhere it was measured)
+    // (four waves per workgroup: the eight-wave form lost everywhere it was measured; rows: 0 or an even value in 40 .. 128 — what pk_rows can
+    // return and the tests run)
+    if (!pk_rows_allowed(rows) || (waves != 0 && waves != 4)) return -1;
     g_pk_rows = rows; return 0;
 }
 
@@ -240,9 +198,7 @@ extern "C" int pcgc_conv_packed64(const int32_t* nbr, int64_t n, const float* in
     static int granted[16] = {0};
     int dev = 0;
     (void)hipGetDevice(&dev);
-    static int cus = 0;
-    if (!cus) { hipDeviceProp_t p; cus = (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256; }
-    const int R = g_pk_rows > 0 ? g_pk_rows : pk_rows(n, cus);
+    const int R = pk_launch_rows(n, pcgc_sched_cus(), g_pk_rows);
     constexpr int nw = 4;
     const int lds = pk_lds(R, nw);
     if (!granted[dev & 15]) {
@@ -252,7 +208,9 @@ extern "C" int pcgc_conv_packed64(const int32_t* nbr, int64_t n, const float* in
         }
         granted[dev & 15] = 1;
     }
-    hipLaunchKernelGGL(k_conv_packed64<4>, dim3(grid_for(n, R)), dim3(256), lds, S(stream), nbr, n, in, in_ld, table, bias, relu, out, out_ld, R);
+    const unsigned grid = pk_launch_grid(n, R);
+    pcgc_sched_record(grid, grid, R);                           // (one tile of R rows per workgroup)
+    hipLaunchKernelGGL(k_conv_packed64<4>, dim3(grid), dim3(256), lds, S(stream), nbr, n, in, in_ld, table, bias, relu, out, out_ld, R);
     PCGC_CHECK_LAUNCH("conv_packed64");
     return 0;
 }

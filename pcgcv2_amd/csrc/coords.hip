@@ -11,6 +11,35 @@ void pcgc_set_error(const char* fmt, ...) {
 extern "C" const char* pcgc_last_error(void) { return g_err; }
 extern "C" int pcgc_version(void) { return 1; }
 
+// ---- the CU count every launcher sizes its grid by, and the record of the last tiled launch (tests of the tile schedules) ------------
+static int g_sched_cus = 0;                                      // 0 = the device's own count
+static thread_local int64_t t_last_sched[3] = {0, 0, 0};
+extern "C" int pcgc_set_sched_cus(int cus) {
+    if (cus < 0) return -1;
+    g_sched_cus = cus; return 0;
+}
+extern "C" int pcgc_last_sched(int64_t out[3]) {
+    if (!out) return -1;
+    for (int i = 0; i < 3; ++i) out[i] = t_last_sched[i];
+    return 0;
+}
+void pcgc_sched_record(int64_t units, int64_t workgroups, int64_t third) {
+    t_last_sched[0] = units; t_last_sched[1] = workgroups; t_last_sched[2] = third;
+}
+int pcgc_sched_cus(void) {
+    if (g_sched_cus > 0) return g_sched_cus;
+    static int by_dev[64] = {0};                                 // (a racing first call stores the same value twice)
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    int cus = (dev >= 0 && dev < 64) ? by_dev[dev] : 0;
+    if (!cus) {
+        hipDeviceProp_t p;
+        cus = (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256;
+        if (dev >= 0 && dev < 64) by_dev[dev] = cus;
+    }
+    return cus;
+}
+
 extern "C" int64_t pcgc_hash_capacity(int64_t n) {
     int64_t cap = 1024;
     while (cap < 2 * n) cap <<= 1;

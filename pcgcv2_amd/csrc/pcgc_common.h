@@ -19,13 +19,12 @@ void pcgc_set_error(const char* fmt, ...);
 static inline hipStream_t S(void* s) { return (hipStream_t)s; }
 static inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 
-// XCD-aware tile order: workgroup b is observed to run on XCD b % 8 (each XCD has its own 4 MiB L2).  Remap so every XCD
-// walks a contiguous slab of tiles: neighbouring tiles gather overlapping rows, which then hit the same L2.  Bijective
-// for any grid size; placement only affects speed, never results.
-__device__ static inline unsigned xcd_tile(unsigned b, unsigned nb) {
-    const unsigned q = nb >> 3, r = nb & 7, x = b & 7;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
-}
+// xcd_tile and the other tile schedules: tile_sched.h (host-compilable, checked on the CPU by tests/native/tile_sched_check.cpp)
+#include "tile_sched.h"
+// coords.hip: the CU count the launchers size their grids by (pcgc_set_sched_cus, else the current device's own), and the record behind
+// pcgc_last_sched (work units, workgroups, waves per workgroup — rows per workgroup for the packed conv — of this thread's last tiled launch)
+int pcgc_sched_cus(void);
+void pcgc_sched_record(int64_t units, int64_t workgroups, int64_t third);
 
 // ---- coordinate key: 4-bit batch | 20-bit z | 20-bit y | 20-bit x ------------------------------------------
 #define PCGC_EMPTY_KEY 0xFFFFFFFFFFFFFFFFull

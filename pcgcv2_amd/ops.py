@@ -381,6 +381,25 @@ def conv_unit_from_coarse(fine, stride_fine, parent_of, coarse_nbr, down, W, bia
     return out
 
 
+def set_sched_cus(cus):
+    """the CU count every launcher sizes its grid by: 0 = the device's own; 1 = persistent grids of 8 workgroups (a few thousand rows reach a
+    second round); 1 << 20 = one tile per wave.  Results never depend on it (tests of the tile schedules, csrc/tile_sched.h)."""
+    check(lib().pcgc_set_sched_cus(int(cus)), 'set_sched_cus')
+
+
+def last_sched():
+    """(work units, workgroups, waves per workgroup) of this thread's most recent persistent tiled launch; after conv_packed64:
+    (tiles, workgroups, rows per workgroup R)"""
+    out = (ctypes.c_int64 * 3)()
+    check(lib().pcgc_last_sched(out), 'last_sched')
+    return tuple(int(v) for v in out)
+
+
+def set_packed_rows(R):
+    """rows per workgroup of conv_packed64: an even value in 40 .. 128, or 0 = chosen per launch (bit-identical results)"""
+    check(lib().pcgc_set_packed_tuning(int(R), 0), 'set_packed_rows')
+
+
 def set_up2_impl(mfma):
     """generative transpose conv kernel for 64->32 / 32->16: 2 fp32 MFMA with LDS-resident fragments (default), 1 fragments from L2, 0 VALU."""
     check(lib().pcgc_set_up2_impl(int(mfma)), 'set_up2_impl')
@@ -453,6 +472,12 @@ def _irn_passes(v, nbr, x, params, ta, tb, passes=(1, 2), t=None):
             rc = PROFILE.launch(wanted, None, None, entry, _p(nbr), m, C, 2, _p(t), C // 2, _p(tb), tb.numel() * 4, P[3], P[7], P[9], _p(x), _ld(x), _p(out), C, s)
         check(rc, v.label)
     return t if out is None else out
+
+
+def irn_form_pass(form, nbr, x, params, tables, ps, t=None):
+    """one pass of the fused block in the form `form` (a key of _IRN: 'rows64', 'rows32', 'rows32_q4', 'child<16>', 'child<32>', 'child_q4') on
+    its own (A/B tools, schedule tests): ps = 1 -> t [n, C/2]; ps = 2 (t given) -> out [n, C]"""
+    return _irn_passes(_IRN[form], nbr, x, params, *tables, passes=(ps,), t=t)
 
 
 def irn_block_rows64(nbr, x, params, tables):

@@ -1165,3 +1165,20 @@ def test_q4x_schedules_counted_waits(tmp_path):
         else:
             assert len(groups) == 81 and nc == 27 and sorted(seen) == [0, 1, 2, 3, 4, 5]
             assert all(g['frag'] == 3 * g['cell'] + j for g, j in zip(groups, [0, 1, 2] * 27))
+
+
+def test_tile_schedules_exhaustive(tmp_path):
+    """The tile schedules of the MFMA kernels (csrc/tile_sched.h: xcd_tile, the persistent tile order of child_tile on every grid the grid rule
+    returns, k_conv_up2_tab's stride loop, the packed conv's tile size) compiled with g++ and checked exhaustively by
+    tests/native/tile_sched_check.cpp: every tile visited exactly once and none outside, grids a non-zero multiple of 8, pk_rows an even R in
+    40 .. 128 whose LDS fits.  Prints the tile sizes the packed conv takes on 256 CUs between 512 and 400 000 rows."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / 'tile_sched_check')
+    subprocess.run(['g++', '-std=c++17', '-O2', '-o', exe, os.path.join(root, 'tests', 'native', 'tile_sched_check.cpp')], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    print(r.stdout)
+    assert r.returncode == 0 and r.stdout.splitlines()[-1] == 'OK', r.stdout[-2000:]
+    sizes = [int(v) for v in next(l for l in r.stdout.splitlines() if l.startswith('pk_rows_256')).split()[1:]]
+    assert sizes and all(40 <= v <= 128 and v % 2 == 0 for v in sizes)
+    assert {64, 94, 60} <= set(sizes)                              # the most frequent size and the two levels of a vox10 frame
