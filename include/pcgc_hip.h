@@ -567,6 +567,52 @@ int pcgc_colour_dist(const uint8_t* cp, int64_t n, const uint8_t* cq, int64_t nq
 size_t pcgc_colour_reduce_workspace_bytes(void);
 int pcgc_colour_reduce(const int64_t* yuv2, const int32_t* rgb2, int64_t n, int64_t* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Colour transform of the attribute stream `_A.bin` (csrc/raht.hip; the definition is tests/raht_reference.py): integer
+ *      lifting RAHT on YCoCg-R over the binary radix tree of the Morton keys.  n = 1 .. 2^24 rows of ONE frame, distinct voxels.  Integer
+ *      arithmetic throughout: every output is exact and the same on every run.  A gap i (0 .. n-2) lies between sorted leaves i and i + 1
+ *      and is one merge of the tree.  Buffers are the caller's; everything runs on `stream`. */
+/* leaves per workgroup of the tile form (form 1) of pcgc_raht_forward / pcgc_raht_inverse */
+int64_t pcgc_raht_tile_leaves(void);
+/* keys [n] (uint64): Morton keys (bit 3 i + 0 / 1 / 2 = bit i of x / y / z; columns 1 .. 3 of coords [n,4]) in ascending order;
+ * perm [n]: sorted leaf i is row perm[i]; status [2] (dev): the number of adjacent equal keys (duplicate voxels), and bit 0 = a coordinate
+ * outside [0, 2^20), bit 1 = a non-zero batch column.  The caller refuses the cloud when either is non-zero.  n > 2^24 is -2 before
+ * anything is touched. */
+size_t pcgc_raht_keys_workspace_bytes(int64_t n);
+int pcgc_raht_keys(const int32_t* coords, int64_t n, uint64_t* keys, int32_t* perm, int32_t* status, void* workspace, size_t workspace_bytes,
+                   void* stream);
+/* per gap: d (uint8) = msb(key_i ^ key_{i+1}); [lo, hi] = the leaves of the merged node (w1 = i - lo + 1, w2 = hi - i); left / right = its
+ * children, a gap index, or ~leaf for a leaf.  order [n-1]: the gaps in coding order (d descending, gap ascending); cross_order [n-1]:
+ * first the gaps whose range crosses a multiple of pcgc_raht_tile_leaves(), in coding order, then the others.  offsets [130] (dev):
+ * bucket [65] then cross [65]; the gaps of split bit d are order[bucket[63 - d] .. bucket[64 - d]), likewise cross_order and cross. */
+size_t pcgc_raht_tree_workspace_bytes(int64_t n);
+int pcgc_raht_tree(const uint64_t* keys, int64_t n, uint8_t* d, int32_t* lo, int32_t* hi, int32_t* left, int32_t* right, int32_t* order,
+                   int32_t* cross_order, int32_t* offsets, void* workspace, size_t workspace_bytes, void* stream);
+/* rgb [n,3] (uint8, the caller's row order) -> H [n-1,3] (int32, per gap: Y, Co, Cg) and val [n,3] (int32) whose row 0 is the DC.
+ * H = a2 - a1, L = a1 + floor(w2 H / (w1 + w2)).  bucket_off [65] on the HOST, cross_off [65] on the device (the two halves of
+ * pcgc_raht_tree's offsets).  form 0: one launch per populated split bit; form 1: tiles in LDS, then the crossing gaps by one workgroup.
+ * Same integers either way. */
+int pcgc_raht_forward(const uint8_t* rgb, const int32_t* perm, int64_t n, const uint8_t* d, const int32_t* lo, const int32_t* hi,
+                      const int32_t* order, const int32_t* bucket_off, const int32_t* cross_order, const int32_t* cross_off, int form,
+                      int32_t* val, int32_t* H, void* stream);
+/* H^ [n-1,3] and the DC -> rgb [n,3] (uint8) in the caller's row order (through perm), clamped to 0 .. 255.  val [n,3]: scratch. */
+int pcgc_raht_inverse(const int32_t* Hhat, int32_t dc_y, int32_t dc_co, int32_t dc_cg, const int32_t* perm, int64_t n, const uint8_t* d,
+                      const int32_t* lo, const int32_t* hi, const int32_t* order, const int32_t* bucket_off, const int32_t* cross_order,
+                      const int32_t* cross_off, int form, int32_t* val, uint8_t* rgb, void* stream);
+/* in coding order, Y, Co, Cg within a gap: tokens [3(n-1)] (int16, 0 .. 63), ctx [3(n-1)] (uint16) = 16 channel + min(d / 3, 15),
+ * escapes (uint16, room for 3(n-1)) = z - 63 of the tokens that are 63, n_escapes [1] (dev), hist [48,64] (int32, dev).
+ * step in sixteenths D16 = 16 (Q = 0) or max(16, isqrt(256 Q^2 (w1 + w2) / (w1 w2))); k = sign(H) (32 |H| + D16) / (2 D16);
+ * z = 2 k (k >= 0) or -2 k - 1. */
+size_t pcgc_raht_quantize_workspace_bytes(int64_t n);
+int pcgc_raht_quantize(const int32_t* H, int64_t n, const uint8_t* d, const int32_t* lo, const int32_t* hi, const int32_t* order, int q_luma,
+                       int q_chroma, int16_t* tokens, uint16_t* ctx, uint16_t* escapes, int32_t* n_escapes, int32_t* hist, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* tokens and escapes -> H^ [n-1,3] per gap = sign(k) (|k| D16 + 8) / 16.  n_escape_tokens [1] (dev) = the tokens that are 63: the caller
+ * refuses a stream whose escape list has another length (escapes past n_escapes read as 0, never past the list). */
+size_t pcgc_raht_dequantize_workspace_bytes(int64_t n);
+int pcgc_raht_dequantize(const int16_t* tokens, const uint16_t* escapes, int64_t n_escapes, int64_t n, const int32_t* lo, const int32_t* hi,
+                         const int32_t* order, int q_luma, int q_chroma, int32_t* Hhat, int32_t* n_escape_tokens, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 /* ---- Estimated surface normals of a voxelised cloud (csrc/normals.hip; nothing in the reference: its D2 figures assume clouds whose normals
  *      another tool estimated).  Per row at voxel p: the neighbourhood is every DISTINCT voxel q of the row's batch with |q - p|^2 <= r2 (p
  *      included); moments [n,10] = k, sum dx dy dz, sum dx^2 dy^2 dz^2 dxdy dxdz dydz over d = q - p (exact); S = k sum(d d^T) - (sum d)(sum d)^T;

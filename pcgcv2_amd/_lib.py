@@ -127,6 +127,17 @@ SIGNATURES = {
     'pcgc_colour_dist': (ci, [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp]),
     'pcgc_colour_reduce_workspace_bytes': (sz, []),
     'pcgc_colour_reduce': (ci, [vp, vp, i64, vp, vp, sz, vp]),
+    'pcgc_raht_tile_leaves': (i64, []),
+    'pcgc_raht_keys_workspace_bytes': (sz, [i64]),
+    'pcgc_raht_keys': (ci, [vp, i64, vp, vp, vp, vp, sz, vp]),
+    'pcgc_raht_tree_workspace_bytes': (sz, [i64]),
+    'pcgc_raht_tree': (ci, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'pcgc_raht_forward': (ci, [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]),
+    'pcgc_raht_inverse': (ci, [vp, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]),
+    'pcgc_raht_quantize_workspace_bytes': (sz, [i64]),
+    'pcgc_raht_quantize': (ci, [vp, i64, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'pcgc_raht_dequantize_workspace_bytes': (sz, [i64]),
+    'pcgc_raht_dequantize': (ci, [vp, vp, i64, i64, vp, vp, vp, ci, ci, vp, vp, vp, sz, vp]),
     'pcgc_normals_ball_masks': (i64, [i32, vp]),
     'pcgc_normals_workspace_bytes': (sz, [i64]),
     'pcgc_normals_estimate': (ci, [vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, i32, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]),

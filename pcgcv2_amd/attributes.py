@@ -1,0 +1,275 @@
+"""Colour codec: `_A.bin`, the colours of one frame on a geometry both sides hold, by an integer lifting form of the region-adaptive
+hierarchical transform (RAHT, the attribute transform of G-PCC) on YCoCg-R (the definition is tests/raht_reference.py).
+
+The transform is exactly invertible, so quantiser 0 returns the colours bit for bit, and it is integer arithmetic throughout, so the
+device kernels (csrc/raht.hip) are held to equality with a numpy definition.  The tree is the binary radix tree of the voxels' Morton
+keys: a function of the geometry alone, built the same way by encoder and decoder.
+
+`_A.bin`, little endian:
+    4s magic "PCGA" | u32 version (1) | u32 N | u16 Q_luma | u16 Q_chroma | 3 x i16 DC (Y, Co, Cg) | u16 R
+    R x (u16 ctx, 63 x u16 cdf[1 .. 63])          the contexts that occur, ascending; cdf[0] = 0 and cdf[64] = 0x10000 are implied
+    u64 tokens = 3 (N - 1) | u64 payload bytes | u64 escapes
+    payload                                        ops.rc_encode_ctx of the tokens in coding order (empty when there is no token)
+    escapes                                        10 bits each, packed LSB first, zero-padded to a byte
+    u32 CRC-32 of all that precedes (ops.crc32)
+The tables are semi-static, per stream: frequencies out of 65536 from the stream's own histogram.  The payload is coded on the host (the
+version field leaves room for a device-coded payload).
+
+    python -m pcgcv2_amd.attributes --filedir CLOUD.ply --qstep Q [--qstep_chroma Qc] [--outdir DIR]
+"""
+import os
+import struct
+import time
+
+import numpy as np
+import torch
+
+from . import ops
+from ._lib import PcgcError
+from .coder import _dump, _slurp
+
+SUFFIX = '_A.bin'
+MAGIC, VERSION = b'PCGA', 1
+CONTEXTS, TOKENS, ESCAPE, ESCAPE_BITS = ops.RAHT_CONTEXTS, 64, ops.RAHT_ESCAPE, 10
+_HEAD = struct.Struct('<4sIIHH3hH')
+_ROW = 2 + 2 * (TOKENS - 1)
+_SIZES = struct.Struct('<3Q')
+
+
+def frequency_rows(hist):
+    """histogram int [48,64] -> (contexts that occur, uint16 [48,65] table in rc_encode_ctx's convention: entry 0 is 0, entry 64 stands
+    for 0x10000).  Per row: 0 where the count is 0, else max(1, floor(count 65536 / total)); the difference to 65536 goes to the most
+    frequent token (lowest index on a tie).  Token 63 is counted at least once, so that entry 63 never has to say 0x10000."""
+    hist = np.asarray(hist, np.int64)
+    rows = np.flatnonzero(hist.sum(1) > 0)
+    table = np.zeros((CONTEXTS, TOKENS + 1), np.uint16)
+    if rows.size:
+        c = hist[rows].copy()
+        c[:, ESCAPE] = np.maximum(c[:, ESCAPE], 1)
+        f = np.where(c > 0, np.maximum(1, (c * 65536) // c.sum(1, keepdims=True)), 0)
+        f[np.arange(rows.size), np.argmax(c, 1)] += 65536 - f.sum(1)
+        table[rows, 1:] = (np.cumsum(f, 1) & 0xFFFF).astype(np.uint16)
+    return [int(r) for r in rows], table
+
+
+def contexts(bucket):
+    """the context of every token in coding order, from the 65 bucket offsets of the tree alone (the gaps of split bit d are positions
+    bucket[63 - d] .. bucket[64 - d]) -> uint16 [3 (N - 1)]"""
+    d = np.repeat(63 - np.arange(64), np.diff(np.asarray(bucket, np.int64)))
+    return (16 * np.arange(3)[None, :] + np.minimum(d // 3, 15)[:, None]).reshape(-1).astype(np.uint16)
+
+
+def _pack_escapes(esc):
+    bits = ((np.asarray(esc, np.uint16)[:, None] >> np.arange(ESCAPE_BITS, dtype=np.uint16)) & 1).astype(np.uint8).reshape(-1)
+    return np.packbits(bits, bitorder='little').tobytes()
+
+
+def _unpack_escapes(data, count):
+    bits = np.unpackbits(np.frombuffer(data, np.uint8), bitorder='little')
+    if bits[count * ESCAPE_BITS:].any():
+        raise PcgcError('non-zero padding behind the escapes')
+    bits = bits[:count * ESCAPE_BITS].reshape(count, ESCAPE_BITS)
+    return (bits.astype(np.uint16) << np.arange(ESCAPE_BITS, dtype=np.uint16)).sum(1).astype(np.uint16)
+
+
+def _qsteps(qstep, qstep_chroma):
+    ql = int(qstep)
+    qc = ql if qstep_chroma is None else int(qstep_chroma)
+    if not (0 <= ql <= 255 and 0 <= qc <= 255):
+        raise ValueError(f'quantiser steps ({qstep}, {qstep_chroma}): integers in 0 .. 255')
+    return ql, qc
+
+
+def read_stream(path, n, bucket):
+    """The host side of decoding: reads `_A.bin` for a geometry of n points whose tree has the bucket offsets `bucket`, checks it and
+    decodes the payload -> (q_luma, q_chroma, dc, tokens int16 [3 (n - 1)], escapes uint16 [E]).  PcgcError on bad magic, version or CRC, a
+    length that disagrees with the header, another point count, a non-monotone CDF row, a context that occurs without a row, an escape
+    count that disagrees with the tokens, and whatever ops.rc_decode_ctx refuses."""
+    blob = _slurp(path)
+    if len(blob) < _HEAD.size + _SIZES.size + 4:
+        raise PcgcError(f'{path}: {len(blob)} bytes, shorter than its header')
+    magic, version, n_file, ql, qc, y, co, cg, R = _HEAD.unpack_from(blob, 0)
+    if magic != MAGIC:
+        raise PcgcError(f'{path}: not a colour stream (magic {magic!r})')
+    if version != VERSION:
+        raise PcgcError(f'{path}: version {version}; this decoder reads version {VERSION}')
+    if struct.unpack_from('<I', blob, len(blob) - 4)[0] != ops.crc32(blob[:-4]):
+        raise PcgcError(f'{path}: CRC-32 mismatch (cut, extended or damaged)')
+    if n_file != n:
+        raise PcgcError(f'{path}: coded for {n_file} points; the geometry has {n}')
+    if ql > 255 or qc > 255:
+        raise PcgcError(f'{path}: quantiser steps ({ql}, {qc}) outside 0 .. 255')
+    pos = _HEAD.size + R * _ROW
+    if R > CONTEXTS or len(blob) < pos + _SIZES.size + 4:
+        raise PcgcError(f'{path}: {R} table rows do not fit the file')
+    n_tok, n_pay, n_esc = _SIZES.unpack_from(blob, pos)
+    pos += _SIZES.size
+    if n_tok != 3 * (n - 1):
+        raise PcgcError(f'{path}: {n_tok} tokens declared; {n} points have {3 * (n - 1)}')
+    if n_esc > n_tok or len(blob) != pos + n_pay + (n_esc * ESCAPE_BITS + 7) // 8 + 4:
+        raise PcgcError(f'{path}: {len(blob)} bytes, but the header declares a payload of {n_pay} bytes and {n_esc} escapes')
+    if n_tok == 0 and (n_pay or R):
+        raise PcgcError(f'{path}: a payload or tables without tokens')
+    table = np.zeros((CONTEXTS, TOKENS + 1), np.uint16)
+    rows, last = [], -1
+    for r in range(R):
+        at = _HEAD.size + r * _ROW
+        c = struct.unpack_from('<H', blob, at)[0]
+        if c >= CONTEXTS or c <= last:
+            raise PcgcError(f'{path}: table row {r} names context {c} (rows are ascending, below {CONTEXTS})')
+        cdf = np.frombuffer(blob, '<u2', TOKENS - 1, at + 2)
+        if (np.diff(cdf.astype(np.int64), prepend=0) < 0).any():
+            raise PcgcError(f'{path}: the CDF of context {c} is not monotone')
+        table[c, 1:TOKENS] = cdf
+        rows.append(c)
+        last = c
+    try:
+        esc = _unpack_escapes(blob[pos + n_pay:-4], n_esc)
+    except PcgcError as e:
+        raise PcgcError(f'{path}: {e}') from None
+    ctx = contexts(bucket)
+    missing = sorted(set(np.unique(ctx).tolist()) - set(rows))
+    if missing:
+        raise PcgcError(f'{path}: contexts {missing} occur on this geometry but have no table row')
+    try:
+        tokens = ops.rc_decode_ctx(table, ctx, blob[pos:pos + n_pay]) if ctx.size else np.zeros(0, np.int16)
+    except PcgcError as e:
+        raise PcgcError(f'{path}: {e}') from None
+    if int(np.count_nonzero(tokens == ESCAPE)) != esc.size:
+        raise PcgcError(f'{path}: {int(np.count_nonzero(tokens == ESCAPE))} escape tokens but {esc.size} escapes')
+    return ql, qc, (y, co, cg), tokens, esc
+
+
+class AttributeCoder():
+    """AttributeCoder(filename): encode writes `filename + postfix + '_A.bin'`, decode reads it.  One frame per call: coordinates are
+    int32 [N,4] device rows (0, x, y, z) of distinct voxels (or [N,3] rows (x, y, z)); a batch, duplicates or coordinates outside
+    [0, 2^20) are a ValueError.  form: ops.RAHT_FORMS (None: ops.RAHT_FORM); the bytes and colours do not depend on it."""
+
+    def __init__(self, filename, form=None):
+        self.filename = filename
+        self.form = form
+        self.times = None                         # measurement hook (tools/attributes_time.py): a dict -> seconds per phase, synchronised
+
+    def _tick(self, phase, t0, dev=None):
+        if self.times is None:
+            return 0.0
+        if dev is not None:
+            torch.cuda.synchronize(dev)
+        now = time.perf_counter()
+        if phase is not None:
+            self.times[phase] = self.times.get(phase, 0.0) + now - t0
+        return now
+
+    @staticmethod
+    def _coords(coords):
+        if not torch.is_tensor(coords) or not coords.is_cuda:
+            raise PcgcError('AttributeCoder: coordinates must be a ROCm device tensor (no CPU fallback exists)')
+        if coords.dim() != 2 or coords.shape[1] not in (3, 4):
+            raise ValueError(f'AttributeCoder: coordinates must be [N,4] (batch, x, y, z) or [N,3], got {tuple(coords.shape)}')
+        coords = coords.to(torch.int32)
+        if coords.shape[1] == 3:
+            coords = torch.cat([torch.zeros((coords.shape[0], 1), dtype=torch.int32, device=coords.device), coords], 1)
+        return coords.contiguous()
+
+    def _tree(self, coords, tree):
+        if tree is None:
+            tree = ops.raht_tree(coords, times=self.times)
+        elif tree.n != coords.shape[0]:
+            raise ValueError(f'AttributeCoder: a tree of {tree.n} leaves for {coords.shape[0]} rows')
+        return tree
+
+    @torch.no_grad()
+    def encode(self, coords, rgb, qstep, qstep_chroma=None, postfix='', tree=None):
+        """colours rgb uint8 [N,3] (device) of the rows of coords -> writes `_A.bin`; -> {bits_A, tokens, escapes, payload_bytes, tree}.
+        tree: ops.raht_tree(coords) when the caller holds it already."""
+        ql, qc = _qsteps(qstep, qstep_chroma)
+        coords = self._coords(coords)
+        dev = coords.device
+        with torch.cuda.device(dev):
+            tree = self._tree(coords, tree)
+            t = self._tick(None, 0.0, dev)
+            H, dc = ops.raht_forward(tree, rgb, form=self.form)
+            t = self._tick('forward', t, dev)
+            tokens, ctx, esc, hist = ops.raht_quantize(tree, H, ql, qc)
+            t = self._tick('quantise', t, dev)
+            tokens_h, ctx_h = tokens.cpu().numpy(), ctx.cpu().numpy().view(np.uint16)
+            esc_h, hist_h, dc_h = esc.cpu().numpy().view(np.uint16), hist.cpu().numpy(), dc.cpu().tolist()
+            t = self._tick('copies', t, dev)
+            rows, table = frequency_rows(hist_h)
+            payload = ops.rc_encode_ctx(table, ctx_h, tokens_h) if tokens_h.size else b''
+            blob = _HEAD.pack(MAGIC, VERSION, tree.n, ql, qc, dc_h[0], dc_h[1], dc_h[2], len(rows))
+            blob += b''.join(struct.pack('<H', c) + table[c, 1:TOKENS].astype('<u2').tobytes() for c in rows)
+            blob += _SIZES.pack(tokens_h.size, len(payload), esc_h.size) + payload + _pack_escapes(esc_h)
+            blob += struct.pack('<I', ops.crc32(blob))
+            _dump(self.filename + postfix + SUFFIX, blob)
+            self._tick('host coder', t)
+        return {'bits_A': 8 * len(blob), 'tokens': int(tokens_h.size), 'escapes': int(esc_h.size), 'payload_bytes': len(payload), 'tree': tree}
+
+    @torch.no_grad()
+    def decode(self, coords, postfix='', tree=None):
+        """the colours of `_A.bin` for the rows of coords (the geometry the encoder coded them on) -> uint8 [N,3] device tensor in the row
+        order of coords.  PcgcError on a stream that is cut, extended, damaged or not made for this geometry."""
+        coords = self._coords(coords)
+        dev = coords.device
+        path = self.filename + postfix + SUFFIX
+        with torch.cuda.device(dev):
+            tree = self._tree(coords, tree)
+            t = self._tick(None, 0.0, dev)
+            ql, qc, dc, tokens, esc = read_stream(path, tree.n, tree.bucket)
+            t = self._tick('host coder', t)
+            tokens_d = torch.from_numpy(np.ascontiguousarray(tokens)).to(dev)
+            esc_d = torch.from_numpy(esc.view(np.int16).copy()).to(dev)
+            t = self._tick('copies', t, dev)
+            Hhat = ops.raht_dequantize(tree, tokens_d, esc_d, ql, qc)
+            t = self._tick('dequantise', t, dev)
+            rgb = ops.raht_inverse(tree, Hhat, dc, form=self.form)
+            self._tick('inverse', t, dev)
+        return rgb
+
+
+def attribute_bits(prefix, postfix=''):
+    """bits of `_A.bin` of one coded cloud"""
+    return os.path.getsize(prefix + postfix + SUFFIX) * 8
+
+
+# ------------------------------------------------------------------------------------------------ CLI
+def run(filedir, outdir, qstep, qstep_chroma=None):
+    """colours -> `_A.bin` -> colours on the file's own geometry; prints bits per point and the colour PSNR"""
+    from .coder import device, _Stopwatch
+    from .data_utils import read_ply_ascii_with_colours, write_ply_ascii_geo_rgb
+    from .pc_error import colour_psnr_device, lattice_coords
+    from .sparse import require_gpu
+    require_gpu(device)
+    xyz, rgb = read_ply_ascii_with_colours(filedir)
+    if rgb is None:
+        raise ValueError(f'{filedir} has no colours (red green blue)')
+    os.makedirs(outdir, exist_ok=True)
+    prefix = os.path.join(outdir, os.path.split(filedir)[-1].split('.')[0])
+    print(prefix)
+    a, ca = lattice_coords(xyz, device), torch.from_numpy(rgb).to(device)
+    coder = AttributeCoder(prefix)
+    with _Stopwatch('Enc Time'):
+        record = coder.encode(a, ca, qstep, qstep_chroma)
+    with _Stopwatch('Dec Time'):
+        cb = coder.decode(a)
+    print(f'{SUFFIX}:\t {record["bits_A"]} bits\t {round(record["bits_A"] / len(a), 3)} bpp')
+    metric = colour_psnr_device(a, ca, a, cb)
+    print('Colour PSNR (Y):\t', metric['c[0],PSNRF'])
+    print('Colour PSNR (U, V):\t', metric['c[1],PSNRF'], metric['c[2],PSNRF'])
+    write_ply_ascii_geo_rgb(prefix + '_dec.ply', xyz, cb.cpu().numpy())
+    return record, metric
+
+
+def main(argv=None):
+    import argparse
+    p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument("--filedir", required=True, help="an ASCII PLY of distinct voxels with red green blue")
+    p.add_argument("--qstep", type=int, required=True, help="quantiser step of the luma channel, 0 .. 255 (0: lossless)")
+    p.add_argument("--qstep_chroma", type=int, default=None, help="quantiser step of Co and Cg (default: --qstep)")
+    p.add_argument("--outdir", default='./output')
+    args = p.parse_args(argv)
+    run(args.filedir, args.outdir, args.qstep, args.qstep_chroma)
+
+
+if __name__ == '__main__':
+    main()

@@ -632,7 +632,19 @@ def _parse_cli(argv):
                         "voxel set is the input's, print the bpp of each file")
     p.add_argument("--occupancy_coder", choices=('host', 'device'), default='host',
                    help="with --lossless: who codes _O.bin, the host range coder (version 1) or interleaved rANS on the device (version 2)")
-    return p.parse_args(argv)
+    p.add_argument("--attributes", metavar='Q[,Qc]', default=None,
+                   help="also write _A.bin, the colour stream (attributes.py): the colours of --filedir carried onto the decoded cloud are "
+                        "coded with quantiser step Q (Qc for chroma; 0 .. 255, 0: lossless), decoded again and written to _dec.ply")
+    args = p.parse_args(argv)
+    if args.attributes is not None:
+        try:
+            q = [int(v) for v in args.attributes.split(',')]
+            if not 1 <= len(q) <= 2 or not all(0 <= v <= 255 for v in q):
+                raise ValueError
+        except ValueError:
+            p.error(f'--attributes {args.attributes}: Q or Q,Qc with integers in 0 .. 255')
+        args.attributes = (q[0], q[-1])
+    return args
 
 
 class _Stopwatch:
@@ -664,12 +676,33 @@ def _recolour(filedir, x_dec):
     return cb, colour_psnr_device(a, ca, b, cb, nn=nn)
 
 
+def _code_attributes(filedir, prefix, x_dec, qsteps):
+    """--attributes: the file's colours carried onto the decoded cloud (what the encoder, having decoded its own stream, codes), written to
+    `_A.bin`, and decoded again from that file on the decoded geometry (what a decoder gets) -> (uint8 [n,3] device tensor, the colour
+    columns of the input against the decoded cloud with the decoded colours, bits of `_A.bin`)"""
+    from .attributes import AttributeCoder
+    from .data_utils import read_ply_ascii_with_colours
+    from .pc_error import colour_psnr_device, lattice_coords, nn_both, recolour_device
+    xyz, rgb = read_ply_ascii_with_colours(filedir)
+    if rgb is None:
+        raise ValueError(f'{filedir} has no colours (red green blue): --attributes needs them')
+    b = x_dec.C.detach().contiguous()
+    a, ca = lattice_coords(xyz, b.device), torch.from_numpy(rgb).to(b.device)
+    nn = nn_both(a, b)
+    attribute_coder = AttributeCoder(prefix)
+    record = attribute_coder.encode(b, recolour_device(a, ca, b, nn=nn), *qsteps)
+    cb = attribute_coder.decode(b)
+    return cb, colour_psnr_device(a, ca, b, cb, nn=nn), record['bits_A']
+
+
 def main(argv=None):
     args = _parse_cli(argv)
     if args.lossless:
         from . import lossless
-        lossless.run(args.ckptdir, args.filedir, args.outdir, occupancy_coder=args.occupancy_coder)
+        lossless.run(args.ckptdir, args.filedir, args.outdir, occupancy_coder=args.occupancy_coder, attributes=args.attributes)
         return
+    if args.attributes is not None and args.scaling_factor != 1:
+        raise ValueError('--attributes codes colours on the decoded lattice: it does not combine with --scaling_factor')
     with _Stopwatch('Loading Time', 4, sync=False):
         x = load_sparse_tensor(args.filedir, device)
     os.makedirs(args.outdir, exist_ok=True)
@@ -698,18 +731,22 @@ def main(argv=None):
     print('bits:\t', bits, '\nbpps:\t', bpps)
     print('bits:\t', sum(bits), '\nbpps:\t', sum(bpps).round(3))
 
-    if args.recolour:
+    if args.attributes is not None:
+        with _Stopwatch('Attributes Time'):
+            rgb_dec, colour, bits_a = _code_attributes(args.filedir, prefix, x_dec, args.attributes)
+        print('bits _A.bin:\t', bits_a, '\nbpp _A.bin:\t', round(bits_a / len(x), 3))
+    elif args.recolour:
         with _Stopwatch('Recolour Time'):
             rgb_dec, colour = _recolour(args.filedir, x_dec)
     with _Stopwatch('Write PC Time', sync=False):
-        if args.recolour:
+        if args.recolour or args.attributes is not None:
             write_ply_ascii_geo_rgb(prefix + '_dec.ply', x_dec.C.detach().cpu().numpy()[:, 1:], rgb_dec.cpu().numpy())
         else:
             write_ply_ascii_geo(prefix + '_dec.ply', x_dec.C.detach().cpu().numpy()[:, 1:])
     with _Stopwatch('PC Error Metric Time', sync=False):
         metrics = pc_error(args.filedir, prefix + '_dec.ply', res=args.res, show=False)
     print('D1 PSNR:\t', metrics["mseF,PSNR (p2point)"][0])
-    if args.recolour:
+    if args.recolour or args.attributes is not None:
         print('Colour PSNR (Y):\t', colour['c[0],PSNRF'])
 
 

@@ -658,12 +658,13 @@ extern "C" int64_t pcgc_rc_encode_ctx(const uint16_t* cdf, int R, int Lp, const 
     uint32_t low = 0; uint64_t span = 1ull << 32; uint64_t pending = 0;
     for (int64_t i = 0; i < n; ++i) {
         const uint32_t* row = rows.data() + (size_t)ctx[i] * Lp; const int s = sym[i];
-        const uint32_t c_lo = (uint32_t)((span * row[s]) >> 16), c_hi = (uint32_t)((span * row[s + 1]) >> 16);
+        const uint64_t w_lo = (span * row[s]) >> 16, w_hi = (span * row[s + 1]) >> 16;
+        const uint32_t c_lo = (uint32_t)w_lo, c_hi = (uint32_t)w_hi;
         const uint32_t lo = low + c_lo, hi = low + c_hi - 1;
         const int nshare = clz32(lo ^ hi);
         const int t = clz32((((~lo | hi) << 1) | 1u) & (0xFFFFFFFFu >> nshare));
         low = (uint32_t)((uint64_t)lo << t) & 0x7FFFFFFFu;
-        span = (uint64_t)(c_hi - c_lo) << t;
+        span = (w_hi - w_lo) << t;                         // (64-bit: a symbol that owns its whole row keeps a span of 2^32; 32 bits gave 0)
         if (nshare) {                                      // first shared bit, `pending` copies of its complement, the other shared bits
             const uint32_t bits = (uint32_t)(((uint64_t)lo << nshare) >> 32), first = bits >> (nshare - 1);
             sink.put(first, 1); sink.put_run(first ^ 1u, pending);

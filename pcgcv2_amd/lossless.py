@@ -283,10 +283,11 @@ def same_voxels(a, b):
 
 
 # ------------------------------------------------------------------------------------------------ CLI
-def run(ckptdir, filedir, outdir, occupancy_coder='host', chunk_steps=None):
-    """encode, decode, check set equality, print the bpp of each file and the total"""
-    from .coder import device, _Stopwatch
-    from .data_utils import load_sparse_tensor, write_ply_ascii_geo
+def run(ckptdir, filedir, outdir, occupancy_coder='host', chunk_steps=None, attributes=None):
+    """encode, decode, check set equality, print the bpp of each file and the total.  attributes = (Q, Qc): also `_A.bin`, the file's colours
+    on the decoded (= the input's) voxel set (attributes.py); `_dec.ply` then carries the colours decoded from it."""
+    from .coder import device, _Stopwatch, _code_attributes
+    from .data_utils import load_sparse_tensor, write_ply_ascii_geo, write_ply_ascii_geo_rgb
     from .pcc_model import PCCModel
     x = load_sparse_tensor(filedir, device)
     os.makedirs(outdir, exist_ok=True)
@@ -311,7 +312,13 @@ def run(ckptdir, filedir, outdir, occupancy_coder='host', chunk_steps=None):
     print('bits:\t', sum(bits), '\nbpps:\t', sum(bpps).round(3))
     print('ideal bits of _O.bin:\t', round(record['est_bits_O'], 1), '\ncandidate rows:\t', record['rows'])
     print('lossless:\t', 'exact' if exact else 'MISMATCH')
-    write_ply_ascii_geo(prefix + '_dec.ply', x_dec.C.detach().cpu().numpy()[:, 1:])
+    if attributes is not None:
+        rgb_dec, colour, bits_a = _code_attributes(filedir, prefix, x_dec, attributes)
+        print('bits _A.bin:\t', bits_a, '\nbpp _A.bin:\t', round(bits_a / len(x), 3))
+        print('Colour PSNR (Y):\t', colour['c[0],PSNRF'])
+        write_ply_ascii_geo_rgb(prefix + '_dec.ply', x_dec.C.detach().cpu().numpy()[:, 1:], rgb_dec.cpu().numpy())
+    else:
+        write_ply_ascii_geo(prefix + '_dec.ply', x_dec.C.detach().cpu().numpy()[:, 1:])
     if not exact:
         raise PcgcError(f'{prefix}: the decoded voxel set differs from the input ({len(x_dec)} against {len(x)} voxels)')
     return record

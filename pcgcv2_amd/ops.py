@@ -1635,6 +1635,153 @@ def colour_reduce(yuv2, rgb2):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ colour transform (csrc/raht.hip)
+RAHT_MAX_POINTS = 1 << 24
+RAHT_CONTEXTS = 48
+RAHT_ESCAPE = 63
+RAHT_FORMS = {'bits': 0, 'tiles': 1}          # one launch per populated split bit | tiles in LDS + the crossing gaps by one workgroup
+RAHT_FORM = 'tiles'                           # the form raht_forward / raht_inverse take unless told otherwise
+
+
+def raht_tile_leaves():
+    return int(lib().pcgc_raht_tile_leaves())
+
+
+class RahtTree:
+    """The binary radix tree of a cloud's Morton keys (pcgc_raht_keys + pcgc_raht_tree): geometry only, shared by the three channels and by
+    encoder and decoder.  Per gap i (between sorted leaves i and i + 1): d, lo, hi, left, right (a gap, or ~leaf); w1 = i - lo + 1,
+    w2 = hi - i.  perm: sorted leaf i is row perm[i] of the caller.  order: the gaps in coding order; bucket: its 65 offsets on the host."""
+    __slots__ = ('n', 'keys', 'perm', 'd', 'lo', 'hi', 'left', 'right', 'order', 'cross_order', 'offsets', 'bucket', 'cross', 'device')
+
+    @property
+    def w1(self):
+        return torch.arange(self.n - 1, dtype=torch.int32, device=self.device) - self.lo + 1
+
+    @property
+    def w2(self):
+        return self.hi - torch.arange(self.n - 1, dtype=torch.int32, device=self.device)
+
+
+def raht_tree(coords, times=None):
+    """coords int32 [n,4] (batch 0, x, y, z in [0, 2^20)) of ONE frame of distinct voxels -> RahtTree.  ValueError for a batch, coordinates
+    out of range, duplicates, an empty cloud or more than 2^24 rows.  times (measurement hook): a dict -> seconds of 'keys + sort' and
+    'tree' added to it, with a synchronisation after each."""
+    import time
+    coords = _i32(coords)
+    if coords.dim() != 2 or coords.shape[1] != 4:
+        raise ValueError(f'raht_tree: coordinates must be [n,4], got {tuple(coords.shape)}')
+    n, dev = coords.shape[0], coords.device
+    if not 1 <= n <= RAHT_MAX_POINTS:
+        raise ValueError(f'raht_tree: {n} rows; the colour transform takes 1 .. 2^24')
+    t = RahtTree()
+    t.n, t.device = n, dev
+    g = max(n - 1, 1)
+    t.keys = torch.empty(n, dtype=torch.int64, device=dev)
+    t.perm = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    ws_bytes = max(int(lib().pcgc_raht_keys_workspace_bytes(n)), int(lib().pcgc_raht_tree_workspace_bytes(n)))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    s = _stream(coords)
+
+    def tick(phase, t0):
+        if times is None:
+            return 0.0
+        torch.cuda.synchronize(dev)
+        now = time.perf_counter()
+        if phase is not None:
+            times[phase] = times.get(phase, 0.0) + now - t0
+        return now
+
+    t0 = tick(None, 0.0)
+    check(lib().pcgc_raht_keys(_p(coords), n, _p(t.keys), _p(t.perm), _p(status), _p(ws), ws_bytes, s), 'raht_keys')
+    t0 = tick('keys + sort', t0)
+    t.d =torch.empty(g, dtype=torch.uint8, device=dev)[:n - 1]
+    t.lo, t.hi, t.left, t.right, t.order, t.cross_order = (torch.empty(g, dtype=torch.int32, device=dev)[:n - 1] for _ in range(6))
+    t.offsets = torch.empty(130, dtype=torch.int32, device=dev)
+    check(lib().pcgc_raht_tree(_p(t.keys), n, _p(t.d), _p(t.lo), _p(t.hi), _p(t.left), _p(t.right), _p(t.order), _p(t.cross_order),
+                               _p(t.offsets), _p(ws), ws_bytes, s), 'raht_tree')
+    dups, flags = status.cpu().tolist()
+    if flags & 2:
+        raise ValueError('raht_tree: the colour transform codes one frame at a time; got rows with a non-zero batch index')
+    if flags & 1:
+        raise ValueError('raht_tree: coordinates outside [0, 2^20)')
+    if dups:
+        raise ValueError(f'raht_tree: {dups} duplicate voxels; the colour transform needs distinct voxels')
+    off = t.offsets.cpu().numpy()
+    tick('tree', t0)
+    t.bucket, t.cross =np.ascontiguousarray(off[:65]), np.ascontiguousarray(off[65:])
+    return t
+
+
+def _raht_form(form):
+    form = RAHT_FORM if form is None else form
+    if form not in RAHT_FORMS:
+        raise ValueError(f'raht form {form!r}: one of {sorted(RAHT_FORMS)}')
+    return RAHT_FORMS[form]
+
+
+def raht_forward(tree, rgb, form=None):
+    """rgb uint8 [n,3] in the row order of the tree's coordinates -> (H int32 [n-1,3] per gap, DC int32 [3]); form: RAHT_FORMS"""
+    rgb = _u8(rgb, 'raht_forward: colours')
+    if rgb.dim() != 2 or tuple(rgb.shape) != (tree.n, 3):
+        raise ValueError(f'raht_forward: colours must be [{tree.n},3], got {tuple(rgb.shape)}')
+    val = torch.empty((tree.n, 3), dtype=torch.int32, device=tree.device)
+    H = torch.empty((max(tree.n - 1, 1), 3), dtype=torch.int32, device=tree.device)[:tree.n - 1]
+    check(lib().pcgc_raht_forward(_p(rgb), _p(tree.perm), tree.n, _p(tree.d), _p(tree.lo), _p(tree.hi), _p(tree.order), tree.bucket.ctypes.data,
+                                  _p(tree.cross_order), _p(tree.offsets) + 65 * 4, _raht_form(form), _p(val), _p(H), _stream(rgb)), 'raht_forward')
+    return H, val[0].clone()
+
+
+def raht_quantize(tree, H, q_luma, q_chroma):
+    """-> (tokens int16 [3(n-1)], ctx uint16 as int16 storage [3(n-1)], escapes uint16-valued int16 [E], hist int32 [48,64]) on the device,
+    in coding order"""
+    n, dev = tree.n, tree.device
+    t = max(3 * (n - 1), 1)
+    tokens = torch.empty(t, dtype=torch.int16, device=dev)[:3 * (n - 1)]
+    ctx = torch.empty(t, dtype=torch.int16, device=dev)[:3 * (n - 1)]
+    esc = torch.empty(t, dtype=torch.int16, device=dev)
+    n_esc = torch.empty(1, dtype=torch.int32, device=dev)
+    hist = torch.empty((RAHT_CONTEXTS, 64), dtype=torch.int32, device=dev)
+    ws_bytes = int(lib().pcgc_raht_quantize_workspace_bytes(n))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    check(lib().pcgc_raht_quantize(_p(_dev(H, torch.int32, 'raht_quantize: H')), n, _p(tree.d), _p(tree.lo), _p(tree.hi), _p(tree.order),
+                                   int(q_luma), int(q_chroma), _p(tokens), _p(ctx), _p(esc), _p(n_esc), _p(hist), _p(ws), ws_bytes, _stream(H)),
+          'raht_quantize')
+    return tokens, ctx, esc[:int(n_esc.item())], hist
+
+
+def raht_dequantize(tree, tokens, escapes, q_luma, q_chroma):
+    """tokens int16 [3(n-1)] and escapes (int16 storage) on the device -> H^ int32 [n-1,3].  PcgcError when the number of escape tokens is
+    not the length of the escape list."""
+    n, dev = tree.n, tree.device
+    if tokens.shape[0] != 3 * (n - 1):
+        raise PcgcError(f'raht_dequantize: {tokens.shape[0]} tokens for {n} points')
+    Hhat = torch.empty((max(n - 1, 1), 3), dtype=torch.int32, device=dev)[:n - 1]
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    ws_bytes = int(lib().pcgc_raht_dequantize_workspace_bytes(n))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    tokens, escapes = _dev(tokens, torch.int16, 'raht_dequantize: tokens'), _dev(escapes, torch.int16, 'raht_dequantize: escapes')
+    check(lib().pcgc_raht_dequantize(_p(tokens), _p(escapes) if escapes.shape[0] else None, escapes.shape[0], n, _p(tree.lo), _p(tree.hi),
+                                     _p(tree.order), int(q_luma), int(q_chroma), _p(Hhat), _p(count), _p(ws), ws_bytes, _stream(tokens)),
+          'raht_dequantize')
+    if int(count.item()) != escapes.shape[0]:
+        raise PcgcError(f'raht_dequantize: {int(count.item())} escape tokens but {escapes.shape[0]} escapes')
+    return Hhat
+
+
+def raht_inverse(tree, Hhat, dc, form=None):
+    """H^ int32 [n-1,3] and the DC (three ints) -> rgb uint8 [n,3] in the row order of the tree's coordinates"""
+    val = torch.empty((tree.n, 3), dtype=torch.int32, device=tree.device)
+    rgb = torch.empty((tree.n, 3), dtype=torch.uint8, device=tree.device)
+    if tuple(Hhat.shape) != (tree.n - 1, 3):
+        raise ValueError(f'raht_inverse: H^ must be [{tree.n - 1},3], got {tuple(Hhat.shape)}')
+    dc = [int(v) for v in dc]
+    check(lib().pcgc_raht_inverse(_p(_dev(Hhat, torch.int32, 'raht_inverse: H^')), dc[0], dc[1], dc[2], _p(tree.perm), tree.n, _p(tree.d),
+                                  _p(tree.lo), _p(tree.hi), _p(tree.order), tree.bucket.ctypes.data, _p(tree.cross_order),
+                                  _p(tree.offsets) + 65 * 4, _raht_form(form), _p(val), _p(rgb), _stream(Hhat)), 'raht_inverse')
+    return rgb
+
+
 # ------------------------------------------------------------------------------------------------ estimated normals (csrc/normals.hip)
 NORMALS_MAX_R2 = 64
 _NORMALS_BALL = {}
