@@ -109,7 +109,9 @@ _sys.modules[__name__].__class__ = _OpsModule
 
 # ------------------------------------------------------------------------------------------------ hash / coords
 class HashTable:
-    """Coordinate hash of one level (keys/vals device buffers + the stride its spatial blocking was built with)."""
+    """Coordinate hash of one level (keys/vals device buffers + the stride its spatial blocking was built with).  Defined: WHICH slots are
+    occupied, WHICH keys are stored and what every lookup returns.  Not defined: which of two keys of one probe chain holds the earlier slot
+    (the order their compare-and-swaps arrive in) — the raw keys / vals arrays of two builds of one level may differ there."""
 
     def __init__(self, coords, stride, keep_last=False):
         n = coords.shape[0]
