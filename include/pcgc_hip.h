@@ -613,6 +613,48 @@ int pcgc_raht_dequantize(const int16_t* tokens, const uint16_t* escapes, int64_t
                          const int32_t* order, int q_luma, int q_chroma, int32_t* Hhat, int32_t* n_escape_tokens, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ---- Colour codec, `_A.bin` version 2 (csrc/attribute_rans.hip; the definition is tests/attr_rans_reference.py): the tokens
+ *      of pcgc_raht_quantize coded ON THE DEVICE by interleaved rANS, the coder of `_O.bin` version 2 above with a 64-ary token in place of
+ *      a bit.  One wave per chunk of 64 S tokens; 64 independent states, one per lane, share one stream of 32-bit words.  The payload,
+ *      little endian:
+ *          u32 S             steps per chunk, 1 .. 2^24
+ *          u32 K             chunks = ceil(tokens / (64 S))
+ *          K x 64 x u64      the decoder's initial state of every lane, chunk by chunk, lane 0 .. 63
+ *          K x u32           W_k: 32-bit words of chunk k
+ *          u32 words         chunk 0's W_0 words, then chunk 1's, ...
+ *      (no token: the payload is empty and nothing is launched; the entries below take n >= 1).
+ *      Chunk k covers tokens [64 S k, min(tokens, 64 S (k + 1))) in coding order; lane j codes tokens base + 64 t + j, t = 0 .. S - 1.
+ *      64-bit state, L = 2^31.  table [48][65] (uint16, dev) in rc_encode_ctx's convention: cdf[ctx][0] = 0 and cdf[ctx][64] = 65536
+ *      whatever entries 0 and 64 say; token a under ctx has c = cdf[ctx][a], f = cdf[ctx][a + 1] - c.
+ *      Encoder, per chunk: every lane starts at x = L; steps t = S - 1 .. 0, lanes j = 63 .. 0 within a step, tokens past the end skipped;
+ *      at a token: if x >= f << 47, emit x & 0xffffffff and x >>= 32; then x = ((x / f) << 16) + x % f + c.  The stream is the emitted
+ *      words in reverse order; the final x of each lane is its stored state (a lane without tokens stores L).  f = 65536 (a token that owns
+ *      its row) is legal: it never emits and leaves x as it is.  f = 1 costs sixteen bits.
+ *      Decoder, per chunk: steps t = 0 .. S - 1, lanes j = 0 .. 63; at a token: s = x & 0xffff, a = the token with cdf[a] <= s < cdf[a + 1]
+ *      (the number of entries 1 .. 63 that are <= s), x = f (x >> 16) + s - c; if x < L, x = x << 32 | next word (within a step, words go
+ *      to the renormalising lanes in ascending lane order).  A chunk is sound iff every stored state is in [2^31, 2^63), exactly W_k words
+ *      were consumed and every lane ends at x == L; a word index at or past W_k reads as 0 and marks the chunk unsound.  The decoder reads
+ *      nothing outside a chunk's words and the table, and writes tokens in 0 .. 63 only, whatever the bytes say.
+ *      tokens < 2^31.  workspace: pcgc_attr_rans_workspace_bytes(n, steps) device bytes, 8-byte aligned (no allocation inside); an entry
+ *      given less refuses with -2 before anything is launched. ---- */
+int64_t pcgc_attr_rans_workspace_bytes(int64_t n, int steps);
+/* ctx and tokens [dev n] as pcgc_raht_quantize writes them -> payload [dev, 8-byte aligned, capacity >= 8 + 516 K + 4 n bytes] in the layout
+ * above; host2 [host 2] = the payload's length in bytes, and the number of tokens that could not be coded (a token outside 0 .. 63, a context
+ * outside 0 .. 47, f <= 0: they are skipped, nothing is divided by 0, and the payload is not a stream): ONE small synchronising copy.  The
+ * caller then copies the finished payload. */
+int pcgc_attr_rans_encode(const uint16_t* table /*[dev 48,65]*/, const uint16_t* ctx /*[dev n]*/, const int16_t* tokens /*[dev n]*/, int64_t n,
+                          int steps, uint8_t* payload, size_t payload_capacity, int64_t* host2, void* workspace, size_t workspace_bytes,
+                          void* stream);
+/* bucket [dev 65]: the first half of pcgc_raht_tree's offsets; token 3 p + channel of the coding order has ctx = 16 channel + min(d / 3, 15)
+ * with d = 63 - (the last b with bucket[b] <= p), computed here on the device.  payload [dev, 8-byte aligned] of payload_bytes bytes whose
+ * head the caller has read: steps = its S, and its K, the table sizes and the sum of W_k agree with n and payload_bytes
+ * (ops.attr_rans_layout checks them on the host; here K follows from n and steps, and no access leaves the payload in any case).  The rows of
+ * `table` that occur are monotone (attributes.read_stream refuses a file whose rows are not)
+ * -> tokens [dev n] (int16, 0 .. 63); host2 [host 2] = tokens that are 63, unsound chunks (0: the payload is sound), in one small copy. */
+int pcgc_attr_rans_decode(const uint16_t* table /*[dev 48,65]*/, const int32_t* bucket /*[dev 65]*/, int64_t n, const uint8_t* payload,
+                          int64_t payload_bytes, int steps, int16_t* tokens /*[dev n]*/, int64_t* host2, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 /* ---- Estimated surface normals of a voxelised cloud (csrc/normals.hip; nothing in the reference: its D2 figures assume clouds whose normals
  *      another tool estimated).  Per row at voxel p: the neighbourhood is every DISTINCT voxel q of the row's batch with |q - p|^2 <= r2 (p
  *      included); moments [n,10] = k, sum dx dy dz, sum dx^2 dy^2 dz^2 dxdy dxdz dydz over d = q - p (exact); S = k sum(d d^T) - (sum d)(sum d)^T;

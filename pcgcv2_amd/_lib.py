@@ -96,6 +96,9 @@ SIGNATURES = {
     'pcgc_occ_rans_workspace_bytes': (sz, [i64, ci]),
     'pcgc_occ_rans_encode': (ci, [vp, i64, ci, vp, vp, sz, vp, vp, sz, vp]),
     'pcgc_occ_rans_decode': (ci, [vp, i64, vp, i64, ci, vp, vp, vp, sz, vp]),
+    'pcgc_attr_rans_workspace_bytes': (i64, [i64, ci]),
+    'pcgc_attr_rans_encode': (ci, [vp, vp, vp, i64, ci, vp, sz, vp, vp, sz, vp]),
+    'pcgc_attr_rans_decode': (ci, [vp, vp, i64, vp, i64, ci, vp, vp, vp, sz, vp]),
     'pcgc_conv_wgrad_workspace_bytes': (sz, [ci, i64, ci, ci]),
     'pcgc_conv_wgrad_rows_per_group': (i64, [ci, i64, ci, ci]),
     'pcgc_conv_wgrad': (ci, [vp, ci, i64, vp, i64, ci, ci, vp, ci, ci, vp, vp, vp, sz, vp]),

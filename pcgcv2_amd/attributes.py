@@ -6,16 +6,22 @@ device kernels (csrc/raht.hip) are held to equality with a numpy definition.  Th
 keys: a function of the geometry alone, built the same way by encoder and decoder.
 
 `_A.bin`, little endian:
-    4s magic "PCGA" | u32 version (1) | u32 N | u16 Q_luma | u16 Q_chroma | 3 x i16 DC (Y, Co, Cg) | u16 R
+    4s magic "PCGA" | u32 version (1 or 2) | u32 N | u16 Q_luma | u16 Q_chroma | 3 x i16 DC (Y, Co, Cg) | u16 R
     R x (u16 ctx, 63 x u16 cdf[1 .. 63])          the contexts that occur, ascending; cdf[0] = 0 and cdf[64] = 0x10000 are implied
     u64 tokens = 3 (N - 1) | u64 payload bytes | u64 escapes
-    payload                                        ops.rc_encode_ctx of the tokens in coding order (empty when there is no token)
+    payload                                        the tokens in coding order (empty when there is no token)
+                                                   version 1: ops.rc_encode_ctx, coded on the host (attribute_coder='host', the default)
+                                                   version 2: ops.attr_rans_encode, interleaved rANS coded on the device
+                                                   (attribute_coder='device'):  u32 S | u32 K = ceil(tokens / (64 S)) | K x 64 x u64 initial
+                                                   decoder states | K x u32 W_k | the chunks' 32-bit words (include/pcgc_hip.h; DESIGN.md 8k;
+                                                   the definition is tests/attr_rans_reference.py)
     escapes                                        10 bits each, packed LSB first, zero-padded to a byte
     u32 CRC-32 of all that precedes (ops.crc32)
-The tables are semi-static, per stream: frequencies out of 65536 from the stream's own histogram.  The payload is coded on the host (the
-version field leaves room for a device-coded payload).
+The tables are semi-static, per stream: frequencies out of 65536 from the stream's own histogram.  The two versions differ in the version
+field and the payload alone; a decoder reads either, whatever coder it was made with.  In version 2 the tokens and their contexts never
+cross the bus: the encoder copies down the histogram, the DC and the escapes, the decoder copies up the tables, the payload and the escapes.
 
-    python -m pcgcv2_amd.attributes --filedir CLOUD.ply --qstep Q [--qstep_chroma Qc] [--outdir DIR]
+    python -m pcgcv2_amd.attributes --filedir CLOUD.ply --qstep Q [--qstep_chroma Qc] [--outdir DIR] [--attribute_coder device [--chunk_steps S]]
 """
 import os
 import struct
@@ -30,6 +36,9 @@ from .coder import _dump, _slurp
 
 SUFFIX = '_A.bin'
 MAGIC, VERSION = b'PCGA', 1
+VERSION_DEVICE = 2                                # payload coded by ops.attr_rans_encode
+CODERS = {'host': VERSION, 'device': VERSION_DEVICE}
+CHUNK_STEPS = 4096                                # steps per chunk of the device coder; 0: one chunk
 CONTEXTS, TOKENS, ESCAPE, ESCAPE_BITS = ops.RAHT_CONTEXTS, 64, ops.RAHT_ESCAPE, 10
 _HEAD = struct.Struct('<4sIIHH3hH')
 _ROW = 2 + 2 * (TOKENS - 1)
@@ -80,19 +89,19 @@ def _qsteps(qstep, qstep_chroma):
     return ql, qc
 
 
-def read_stream(path, n, bucket):
-    """The host side of decoding: reads `_A.bin` for a geometry of n points whose tree has the bucket offsets `bucket`, checks it and
-    decodes the payload -> (q_luma, q_chroma, dc, tokens int16 [3 (n - 1)], escapes uint16 [E]).  PcgcError on bad magic, version or CRC, a
-    length that disagrees with the header, another point count, a non-monotone CDF row, a context that occurs without a row, an escape
-    count that disagrees with the tokens, and whatever ops.rc_decode_ctx refuses."""
+def read_container(path, n, bucket, versions=(VERSION, VERSION_DEVICE)):
+    """Every check of `_A.bin` that needs neither the decoded tokens nor the device, for a geometry of n points whose tree has the bucket
+    offsets `bucket` -> (version, q_luma, q_chroma, dc, table uint16 [48,65], payload bytes, escapes uint16 [E]).  PcgcError on bad magic,
+    a version not in `versions`, a bad CRC, a length that disagrees with the header, another point count, a non-monotone CDF row and a
+    context that occurs without a row."""
     blob = _slurp(path)
     if len(blob) < _HEAD.size + _SIZES.size + 4:
         raise PcgcError(f'{path}: {len(blob)} bytes, shorter than its header')
     magic, version, n_file, ql, qc, y, co, cg, R = _HEAD.unpack_from(blob, 0)
     if magic != MAGIC:
         raise PcgcError(f'{path}: not a colour stream (magic {magic!r})')
-    if version != VERSION:
-        raise PcgcError(f'{path}: version {version}; this decoder reads version {VERSION}')
+    if version not in versions:
+        raise PcgcError(f'{path}: version {version}; this decoder reads version {" and ".join(str(v) for v in versions)}')
     if struct.unpack_from('<I', blob, len(blob) - 4)[0] != ops.crc32(blob[:-4]):
         raise PcgcError(f'{path}: CRC-32 mismatch (cut, extended or damaged)')
     if n_file != n:
@@ -127,27 +136,49 @@ def read_stream(path, n, bucket):
         esc = _unpack_escapes(blob[pos + n_pay:-4], n_esc)
     except PcgcError as e:
         raise PcgcError(f'{path}: {e}') from None
-    ctx = contexts(bucket)
-    missing = sorted(set(np.unique(ctx).tolist()) - set(rows))
+    levels = np.minimum((63 - np.flatnonzero(np.diff(np.asarray(bucket, np.int64)) > 0)) // 3, 15)
+    missing = sorted({int(16 * ch + lv) for ch in range(3) for lv in levels} - set(rows))
     if missing:
         raise PcgcError(f'{path}: contexts {missing} occur on this geometry but have no table row')
+    return version, ql, qc, (y, co, cg), table, blob[pos:pos + n_pay], esc
+
+
+def read_stream(path, n, bucket):
+    """The host side of decoding a version-1 file: read_container's checks, then the payload decoded by ops.rc_decode_ctx ->
+    (q_luma, q_chroma, dc, tokens int16 [3 (n - 1)], escapes uint16 [E]).  PcgcError also on an escape count that disagrees with the
+    tokens, and on whatever ops.rc_decode_ctx refuses."""
+    _, ql, qc, dc, table, payload, esc = read_container(path, n, bucket, versions=(VERSION,))
+    return ql, qc, dc, _host_tokens(path, table, bucket, payload, esc), esc
+
+
+def _host_tokens(path, table, bucket, payload, esc):
+    """the tokens of a version-1 payload that read_container has passed -> int16 [3 (n - 1)]"""
+    ctx = contexts(bucket)
     try:
-        tokens = ops.rc_decode_ctx(table, ctx, blob[pos:pos + n_pay]) if ctx.size else np.zeros(0, np.int16)
+        tokens = ops.rc_decode_ctx(table, ctx, payload) if ctx.size else np.zeros(0, np.int16)
     except PcgcError as e:
         raise PcgcError(f'{path}: {e}') from None
     if int(np.count_nonzero(tokens == ESCAPE)) != esc.size:
         raise PcgcError(f'{path}: {int(np.count_nonzero(tokens == ESCAPE))} escape tokens but {esc.size} escapes')
-    return ql, qc, (y, co, cg), tokens, esc
+    return tokens
 
 
 class AttributeCoder():
     """AttributeCoder(filename): encode writes `filename + postfix + '_A.bin'`, decode reads it.  One frame per call: coordinates are
     int32 [N,4] device rows (0, x, y, z) of distinct voxels (or [N,3] rows (x, y, z)); a batch, duplicates or coordinates outside
-    [0, 2^20) are a ValueError.  form: ops.RAHT_FORMS (None: ops.RAHT_FORM); the bytes and colours do not depend on it."""
+    [0, 2^20) are a ValueError.  form: ops.RAHT_FORMS (None: ops.RAHT_FORM); the bytes and colours do not depend on it.
+    attribute_coder: 'host' writes version 1, 'device' version 2 in chunks of 64 x chunk_steps tokens (0: one chunk); decode reads either
+    version whatever these two say."""
 
-    def __init__(self, filename, form=None):
+    def __init__(self, filename, form=None, attribute_coder='host', chunk_steps=CHUNK_STEPS):
+        if attribute_coder not in CODERS:
+            raise ValueError(f'attribute_coder {attribute_coder!r}: one of {sorted(CODERS)}')
+        if isinstance(chunk_steps, bool) or not isinstance(chunk_steps, (int, np.integer)) or not 0 <= chunk_steps <= ops.RANS_MAX_STEPS:
+            raise ValueError(f'chunk_steps {chunk_steps!r}: an integer in 0 .. 2^24 (0: one chunk)')
         self.filename = filename
         self.form = form
+        self.attribute_coder = attribute_coder
+        self.chunk_steps = int(chunk_steps)
         self.times = None                         # measurement hook (tools/attributes_time.py): a dict -> seconds per phase, synchronised
 
     def _tick(self, phase, t0, dev=None):
@@ -192,18 +223,26 @@ class AttributeCoder():
             t = self._tick('forward', t, dev)
             tokens, ctx, esc, hist = ops.raht_quantize(tree, H, ql, qc)
             t = self._tick('quantise', t, dev)
-            tokens_h, ctx_h = tokens.cpu().numpy(), ctx.cpu().numpy().view(np.uint16)
+            device = self.attribute_coder == 'device'
+            n_tok = int(tokens.shape[0])
+            if not device:
+                tokens_h, ctx_h = tokens.cpu().numpy(), ctx.cpu().numpy().view(np.uint16)
             esc_h, hist_h, dc_h = esc.cpu().numpy().view(np.uint16), hist.cpu().numpy(), dc.cpu().tolist()
             t = self._tick('copies', t, dev)
             rows, table = frequency_rows(hist_h)
-            payload = ops.rc_encode_ctx(table, ctx_h, tokens_h) if tokens_h.size else b''
-            blob = _HEAD.pack(MAGIC, VERSION, tree.n, ql, qc, dc_h[0], dc_h[1], dc_h[2], len(rows))
+            if device:                            # the tokens and contexts stay where pcgc_raht_quantize wrote them
+                steps = self.chunk_steps or max(1, ops.attr_rans_chunks(n_tok, 1))
+                payload = ops.attr_rans_encode(table, ctx, tokens, steps)
+                t = self._tick('device coder', t, dev)
+            else:
+                payload = ops.rc_encode_ctx(table, ctx_h, tokens_h) if n_tok else b''
+            blob = _HEAD.pack(MAGIC, CODERS[self.attribute_coder], tree.n, ql, qc, dc_h[0], dc_h[1], dc_h[2], len(rows))
             blob += b''.join(struct.pack('<H', c) + table[c, 1:TOKENS].astype('<u2').tobytes() for c in rows)
-            blob += _SIZES.pack(tokens_h.size, len(payload), esc_h.size) + payload + _pack_escapes(esc_h)
+            blob += _SIZES.pack(n_tok, len(payload), esc_h.size) + payload + _pack_escapes(esc_h)
             blob += struct.pack('<I', ops.crc32(blob))
             _dump(self.filename + postfix + SUFFIX, blob)
             self._tick('host coder', t)
-        return {'bits_A': 8 * len(blob), 'tokens': int(tokens_h.size), 'escapes': int(esc_h.size), 'payload_bytes': len(payload), 'tree': tree}
+        return {'bits_A': 8 * len(blob), 'tokens': n_tok, 'escapes': int(esc_h.size), 'payload_bytes': len(payload), 'tree': tree}
 
     @torch.no_grad()
     def decode(self, coords, postfix='', tree=None):
@@ -215,9 +254,20 @@ class AttributeCoder():
         with torch.cuda.device(dev):
             tree = self._tree(coords, tree)
             t = self._tick(None, 0.0, dev)
-            ql, qc, dc, tokens, esc = read_stream(path, tree.n, tree.bucket)
-            t = self._tick('host coder', t)
-            tokens_d = torch.from_numpy(np.ascontiguousarray(tokens)).to(dev)
+            version, ql, qc, dc, table, payload, esc = read_container(path, tree.n, tree.bucket)
+            if version == VERSION_DEVICE:         # every host check has passed; the tokens are decoded where they are used
+                t = self._tick('host coder', t)
+                try:
+                    tokens_d, n_escape = ops.attr_rans_decode(table, tree, payload, 3 * (tree.n - 1))
+                except PcgcError as e:
+                    raise PcgcError(f'{path}: {e}') from None
+                if n_escape != esc.size:
+                    raise PcgcError(f'{path}: {n_escape} escape tokens but {esc.size} escapes')
+                t = self._tick('device coder', t, dev)
+            else:
+                tokens = _host_tokens(path, table, tree.bucket, payload, esc)
+                t = self._tick('host coder', t)
+                tokens_d = torch.from_numpy(np.ascontiguousarray(tokens)).to(dev)
             esc_d = torch.from_numpy(esc.view(np.int16).copy()).to(dev)
             t = self._tick('copies', t, dev)
             Hhat = ops.raht_dequantize(tree, tokens_d, esc_d, ql, qc)
@@ -233,7 +283,7 @@ def attribute_bits(prefix, postfix=''):
 
 
 # ------------------------------------------------------------------------------------------------ CLI
-def run(filedir, outdir, qstep, qstep_chroma=None):
+def run(filedir, outdir, qstep, qstep_chroma=None, attribute_coder='host', chunk_steps=CHUNK_STEPS):
     """colours -> `_A.bin` -> colours on the file's own geometry; prints bits per point and the colour PSNR"""
     from .coder import device, _Stopwatch
     from .data_utils import read_ply_ascii_with_colours, write_ply_ascii_geo_rgb
@@ -247,7 +297,7 @@ def run(filedir, outdir, qstep, qstep_chroma=None):
     prefix = os.path.join(outdir, os.path.split(filedir)[-1].split('.')[0])
     print(prefix)
     a, ca = lattice_coords(xyz, device), torch.from_numpy(rgb).to(device)
-    coder = AttributeCoder(prefix)
+    coder = AttributeCoder(prefix, attribute_coder=attribute_coder, chunk_steps=chunk_steps)
     with _Stopwatch('Enc Time'):
         record = coder.encode(a, ca, qstep, qstep_chroma)
     with _Stopwatch('Dec Time'):
@@ -267,8 +317,11 @@ def main(argv=None):
     p.add_argument("--qstep", type=int, required=True, help="quantiser step of the luma channel, 0 .. 255 (0: lossless)")
     p.add_argument("--qstep_chroma", type=int, default=None, help="quantiser step of Co and Cg (default: --qstep)")
     p.add_argument("--outdir", default='./output')
+    p.add_argument("--attribute_coder", choices=sorted(CODERS), default='host',
+                   help="host: the payload coded by the host range coder (_A.bin version 1); device: interleaved rANS on the GPU (version 2)")
+    p.add_argument("--chunk_steps", type=int, default=CHUNK_STEPS, help="device coder: steps per chunk of 64 lanes (0: one chunk)")
     args = p.parse_args(argv)
-    run(args.filedir, args.outdir, args.qstep, args.qstep_chroma)
+    run(args.filedir, args.outdir, args.qstep, args.qstep_chroma, args.attribute_coder, args.chunk_steps)
 
 
 if __name__ == '__main__':

@@ -635,6 +635,9 @@ def _parse_cli(argv):
     p.add_argument("--attributes", metavar='Q[,Qc]', default=None,
                    help="also write _A.bin, the colour stream (attributes.py): the colours of --filedir carried onto the decoded cloud are "
                         "coded with quantiser step Q (Qc for chroma; 0 .. 255, 0: lossless), decoded again and written to _dec.ply")
+    p.add_argument("--attribute_coder", choices=('host', 'device'), default='host',
+                   help="with --attributes: who codes the payload of _A.bin, the host range coder (version 1) or interleaved rANS on the "
+                        "device (version 2)")
     args = p.parse_args(argv)
     if args.attributes is not None:
         try:
@@ -676,7 +679,7 @@ def _recolour(filedir, x_dec):
     return cb, colour_psnr_device(a, ca, b, cb, nn=nn)
 
 
-def _code_attributes(filedir, prefix, x_dec, qsteps):
+def _code_attributes(filedir, prefix, x_dec, qsteps, coder='host'):
     """--attributes: the file's colours carried onto the decoded cloud (what the encoder, having decoded its own stream, codes), written to
     `_A.bin`, and decoded again from that file on the decoded geometry (what a decoder gets) -> (uint8 [n,3] device tensor, the colour
     columns of the input against the decoded cloud with the decoded colours, bits of `_A.bin`)"""
@@ -689,7 +692,7 @@ def _code_attributes(filedir, prefix, x_dec, qsteps):
     b = x_dec.C.detach().contiguous()
     a, ca = lattice_coords(xyz, b.device), torch.from_numpy(rgb).to(b.device)
     nn = nn_both(a, b)
-    attribute_coder = AttributeCoder(prefix)
+    attribute_coder = AttributeCoder(prefix, attribute_coder=coder)
     record = attribute_coder.encode(b, recolour_device(a, ca, b, nn=nn), *qsteps)
     cb = attribute_coder.decode(b)
     return cb, colour_psnr_device(a, ca, b, cb, nn=nn), record['bits_A']
@@ -699,7 +702,8 @@ def main(argv=None):
     args = _parse_cli(argv)
     if args.lossless:
         from . import lossless
-        lossless.run(args.ckptdir, args.filedir, args.outdir, occupancy_coder=args.occupancy_coder, attributes=args.attributes)
+        lossless.run(args.ckptdir, args.filedir, args.outdir, occupancy_coder=args.occupancy_coder, attributes=args.attributes,
+                     attribute_coder=args.attribute_coder)
         return
     if args.attributes is not None and args.scaling_factor != 1:
         raise ValueError('--attributes codes colours on the decoded lattice: it does not combine with --scaling_factor')
@@ -733,7 +737,7 @@ def main(argv=None):
 
     if args.attributes is not None:
         with _Stopwatch('Attributes Time'):
-            rgb_dec, colour, bits_a = _code_attributes(args.filedir, prefix, x_dec, args.attributes)
+            rgb_dec, colour, bits_a = _code_attributes(args.filedir, prefix, x_dec, args.attributes, args.attribute_coder)
         print('bits _A.bin:\t', bits_a, '\nbpp _A.bin:\t', round(bits_a / len(x), 3))
     elif args.recolour:
         with _Stopwatch('Recolour Time'):

@@ -283,9 +283,10 @@ def same_voxels(a, b):
 
 
 # ------------------------------------------------------------------------------------------------ CLI
-def run(ckptdir, filedir, outdir, occupancy_coder='host', chunk_steps=None, attributes=None):
+def run(ckptdir, filedir, outdir, occupancy_coder='host', chunk_steps=None, attributes=None, attribute_coder='host'):
     """encode, decode, check set equality, print the bpp of each file and the total.  attributes = (Q, Qc): also `_A.bin`, the file's colours
-    on the decoded (= the input's) voxel set (attributes.py); `_dec.ply` then carries the colours decoded from it."""
+    on the decoded (= the input's) voxel set (attributes.py), its payload coded by attribute_coder ('host' or 'device'); `_dec.ply` then
+    carries the colours decoded from it."""
     from .coder import device, _Stopwatch, _code_attributes
     from .data_utils import load_sparse_tensor, write_ply_ascii_geo, write_ply_ascii_geo_rgb
     from .pcc_model import PCCModel
@@ -313,7 +314,7 @@ def run(ckptdir, filedir, outdir, occupancy_coder='host', chunk_steps=None, attr
     print('ideal bits of _O.bin:\t', round(record['est_bits_O'], 1), '\ncandidate rows:\t', record['rows'])
     print('lossless:\t', 'exact' if exact else 'MISMATCH')
     if attributes is not None:
-        rgb_dec, colour, bits_a = _code_attributes(filedir, prefix, x_dec, attributes)
+        rgb_dec, colour, bits_a = _code_attributes(filedir, prefix, x_dec, attributes, attribute_coder)
         print('bits _A.bin:\t', bits_a, '\nbpp _A.bin:\t', round(bits_a / len(x), 3))
         print('Colour PSNR (Y):\t', colour['c[0],PSNRF'])
         write_ply_ascii_geo_rgb(prefix + '_dec.ply', x_dec.C.detach().cpu().numpy()[:, 1:], rgb_dec.cpu().numpy())

@@ -1784,6 +1784,93 @@ def raht_inverse(tree, Hhat, dc, form=None):
     return rgb
 
 
+# ------------------------------------------------------------------------------------------------ colour codec, device coder (csrc/attribute_rans.hip)
+def attr_rans_chunks(n, steps):
+    """chunks of 64 x steps tokens that n tokens make"""
+    return -(-int(n) // (RANS_LANES * int(steps)))
+
+
+def _attr_table(table, dev):
+    table = np.ascontiguousarray(table, dtype=np.uint16)
+    if table.shape != (RAHT_CONTEXTS, 65):
+        raise PcgcError(f'attr_rans: the table is uint16 [{RAHT_CONTEXTS}, 65], got {table.shape}')
+    return torch.from_numpy(table.view(np.int16)).to(dev)
+
+
+def attr_rans_encode(table, ctx, tokens, steps):
+    """table uint16 [48, 65] (host; rc_encode_ctx's convention: entry 0 is 0, entry 64 stands for 0x10000), ctx (uint16 in int16 storage)
+    and tokens int16 [n] on the device, as raht_quantize returns them -> the payload of `_A.bin` version 2 (include/pcgc_hip.h) as bytes,
+    coded on the device in chunks of 64 x steps tokens; b'' for n = 0, without a launch.  One small synchronising copy (the length) and one
+    copy of the finished payload.  PcgcError on a token outside 0 .. 63, a context outside 0 .. 47 or a token whose frequency is 0."""
+    n, dev, steps = _dev(tokens, torch.int16, 'attr_rans_encode: tokens').shape[0], tokens.device, int(steps)
+    if tokens.dim() != 1 or tuple(_dev(ctx, torch.int16, 'attr_rans_encode: ctx').shape) != (n,) or not 1 <= steps <= RANS_MAX_STEPS:
+        raise PcgcError(f'attr_rans_encode: tokens {tuple(tokens.shape)}, ctx {tuple(ctx.shape)}, {steps} steps per chunk (1 .. 2^24)')
+    table = _attr_table(table, dev)
+    if n == 0:
+        return b''
+    cap = 8 + 516 * attr_rans_chunks(n, steps) + 4 * n
+    out = torch.empty((cap + 7) // 8, dtype=torch.int64, device=dev)
+    nbytes = int(lib().pcgc_attr_rans_workspace_bytes(n, steps))
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    host = np.zeros(2, dtype=np.int64)
+    check(lib().pcgc_attr_rans_encode(_p(table), _p(ctx), _p(tokens), n, steps, _p(out), cap, host.ctypes.data, _p(ws), nbytes, _stream(tokens)),
+          'attr_rans_encode')
+    if host[1]:
+        raise PcgcError(f'attr_rans_encode: {int(host[1])} tokens cannot be coded (outside 0 .. 63, under a context outside 0 .. 47, or of '
+                        'frequency 0 in their row)')
+    return out.view(torch.uint8)[:int(host[0])].cpu().numpy().tobytes()
+
+
+def attr_rans_layout(payload, n):
+    """the host's checks of the payload of `_A.bin` version 2 against its n tokens and its own size -> (S, K).  PcgcError when S is outside
+    1 .. 2^24, K is not ceil(n / (64 S)), the tables do not fit or the word counts do not add up to the byte length; n = 0 takes the empty
+    payload alone -> (0, 0)."""
+    n = int(n)
+    if n == 0:
+        if len(payload):
+            raise PcgcError(f'attr_rans: a payload of {len(payload)} bytes without tokens')
+        return 0, 0
+    if len(payload) < 8:
+        raise PcgcError(f'attr_rans: {len(payload)} bytes, shorter than the head')
+    steps, chunks = (int(v) for v in np.frombuffer(payload, '<u4', 2))
+    if not 1 <= steps <= RANS_MAX_STEPS:
+        raise PcgcError(f'attr_rans: {steps} steps per chunk (1 .. 2^24)')
+    if chunks != attr_rans_chunks(n, steps):
+        raise PcgcError(f'attr_rans: {chunks} chunks declared; {n} tokens in chunks of 64 x {steps} make {attr_rans_chunks(n, steps)}')
+    if len(payload) < 8 + 516 * chunks:
+        raise PcgcError(f'attr_rans: {len(payload)} bytes, cut inside the tables of {chunks} chunks')
+    words = int(np.frombuffer(payload, '<u4', chunks, 8 + 512 * chunks).astype(np.int64).sum())
+    if 8 + 516 * chunks + 4 * words != len(payload):
+        raise PcgcError(f'attr_rans: {len(payload)} bytes, but the chunks declare {words} words in all')
+    return steps, chunks
+
+
+def attr_rans_decode(table, tree, payload, n):
+    """table uint16 [48, 65] (host), tree: the RahtTree of the geometry (its `offsets` on the device give every token's context: they are
+    computed there, never uploaded), payload: bytes of `_A.bin` version 2, n tokens -> (tokens int16 [n] on the device in coding order,
+    the number of tokens that are 63).  The payload goes up in one copy, the two numbers come back in one.  PcgcError on a payload whose S,
+    K or lengths disagree with n and its own size (checked here, before any launch) and on an unsound chunk (the kernel's verdict)."""
+    n, dev = int(n), tree.offsets.device
+    payload = bytes(payload)
+    steps, chunks = attr_rans_layout(payload, n)
+    if _dev(tree.offsets, torch.int32, 'attr_rans_decode: tree offsets').numel() < 65:
+        raise PcgcError('attr_rans_decode: the tree has no bucket offsets')
+    table = _attr_table(table, dev)
+    if n == 0:
+        return torch.empty(0, dtype=torch.int16, device=dev), 0
+    up = torch.frombuffer(bytearray(payload) + bytes(-len(payload) % 8), dtype=torch.int64).to(dev)        # (8-byte aligned on the device)
+    tokens = torch.empty(n, dtype=torch.int16, device=dev)
+    nbytes = int(lib().pcgc_attr_rans_workspace_bytes(n, steps))
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    host = np.zeros(2, dtype=np.int64)
+    check(lib().pcgc_attr_rans_decode(_p(table), _p(tree.offsets), n, _p(up), len(payload), steps, _p(tokens), host.ctypes.data, _p(ws), nbytes,
+                                      _stream(tokens)), 'attr_rans_decode')
+    if host[1]:
+        raise PcgcError(f'attr_rans_decode: unsound payload ({int(host[1])} of {chunks} chunks fail their check: states in [2^31, 2^63), '
+                        'exactly W_k words consumed, every lane back at 2^31)')
+    return tokens, int(host[0])
+
+
 # ------------------------------------------------------------------------------------------------ estimated normals (csrc/normals.hip)
 NORMALS_MAX_R2 = 64
 _NORMALS_BALL = {}

@@ -5,7 +5,11 @@ tree, forward, quantise, copies, host coder; host coder, copies, dequantise, inv
 bit | tiles), the forward and inverse transforms alone in both forms, and for scale: the numpy definition on the same cloud, carrying the
 colours onto the decoded cloud (shared and own searches) and the lossy geometry decode.  With --trace it re-runs itself once under
 `rocprofv3 --kernel-trace --stats` (a fresh child process) and prints the table of the k_raht_ kernels.
-    tools/attributes_time.py [--cloud NAME] [--qstep Q] [--repeat K] [--no-host] [--trace]"""
+    tools/attributes_time.py [--cloud NAME] [--qstep Q] [--repeat K] [--no-host] [--trace]
+With --attribute_coder device it times the device coder of `_A.bin` version 2 instead: version 1 first, then per value of
+--chunk_steps the chunks, the bits of `_A.bin` and their excess over version 1, encode and decode as whole calls and the synchronised time
+of the coder phase, all in this one process, the decoded colours compared with version 1's.
+    tools/attributes_time.py --attribute_coder device [--chunk_steps 1024,4096,16384,0] [--cloud NAME] [--qstep Q] [--repeat K]"""
 import argparse, csv, glob, json, os, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -16,6 +20,8 @@ ap.add_argument('--qstep', type=int, default=8)
 ap.add_argument('--repeat', type=int, default=11)
 ap.add_argument('--no-host', action='store_true', help='skip the numpy definition (seconds on the bench frame)')
 ap.add_argument('--trace', action='store_true', help='also one rocprofv3 --kernel-trace --stats run of two calls per form (child process)')
+ap.add_argument('--attribute_coder', choices=('host', 'device'), default='host', help='device: time the device coder over --chunk_steps instead')
+ap.add_argument('--chunk_steps', default='1024,4096,16384,0', help='with --attribute_coder device: steps per chunk, comma separated (0: one chunk)')
 ap.add_argument('--one-call', action='store_true', help=argparse.SUPPRESS)
 args = ap.parse_args()
 
@@ -86,6 +92,29 @@ def phases(fn, coder):
     out['whole call, no stopwatch'] = median_ms(fn)
     return out
 
+
+if args.attribute_coder == 'device':
+    from pcgcv2_amd.attributes import CHUNK_STEPS
+    report = {'cloud': args.cloud, 'points': len(a), 'tokens': 3 * (len(a) - 1), 'qstep': args.qstep, 'runs': runs, 'form': ops.RAHT_FORM,
+              'default_chunk_steps': CHUNK_STEPS, 'device_coder': []}
+    host = AttributeCoder(prefix + 'v1')
+    report['version_1'] = {'encode_ms': phases(lambda: host.encode(a, ca, args.qstep), host), 'decode_ms': phases(lambda: host.decode(a), host),
+                           'bits_A': 8 * os.path.getsize(prefix + 'v1_A.bin')}
+    want = host.decode(a)
+    for S in [int(v) for v in args.chunk_steps.split(',')]:
+        coder = AttributeCoder(prefix + f'v2_{S}', attribute_coder='device', chunk_steps=S)
+        enc, dec = phases(lambda: coder.encode(a, ca, args.qstep), coder), phases(lambda: coder.decode(a), coder)
+        bits = 8 * os.path.getsize(prefix + f'v2_{S}_A.bin')
+        steps = S or -(-report['tokens'] // 64)
+        report['device_coder'].append({
+            'chunk_steps': S, 'chunks': ops.attr_rans_chunks(report['tokens'], steps), 'bits_A': bits,
+            'excess_over_version_1_percent': round(100.0 * (bits - report['version_1']['bits_A']) / report['version_1']['bits_A'], 3),
+            'encode_ms': enc, 'decode_ms': dec, 'coder_phase_ms': {'encode': enc['device coder'], 'decode': dec['device coder']},
+            'same_colours_as_version_1': bool(torch.equal(coder.decode(a), want)),
+            'faster_than_version_1': {'encode': enc['whole call, no stopwatch'] < report['version_1']['encode_ms']['whole call, no stopwatch'],
+                                      'decode': dec['whole call, no stopwatch'] < report['version_1']['decode_ms']['whole call, no stopwatch']}})
+    print(json.dumps(report, indent=1))
+    raise SystemExit(0)
 
 report = {'cloud': args.cloud, 'points': len(a), 'qstep': args.qstep, 'runs': runs, 'tile_leaves': ops.raht_tile_leaves(),
           'default_form': ops.RAHT_FORM, 'encode_ms': {}, 'decode_ms': {}, 'forward_ms': {}, 'inverse_ms': {}}
