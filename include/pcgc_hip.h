@@ -613,6 +613,47 @@ int pcgc_raht_dequantize(const int16_t* tokens, const uint16_t* escapes, int64_t
                          const int32_t* order, int q_luma, int q_chroma, int32_t* Hhat, int32_t* n_escape_tokens, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ---- The colour transform of a BATCH of 1 .. 16 frames in one pass.  coords [n,4] rows (b, x, y, z) in any order, n = 1 ..
+ *      2^24 rows in all.  The frame index is bits 60 .. 63 of the key (compared unsigned), so after one sort frame b is the run of leaves
+ *      [start_b, start_b + n_b); a gap with d < 60 lies inside one frame and has there the lo, hi and children it has in that frame alone,
+ *      shifted by start_b.  The B - 1 gaps with d >= 60 are frame boundaries: no merge, no token, lo = hi = -1.  Every output of frame b is
+ *      what the single-frame entries above give for its rows alone. ---- */
+/* status [34] (dev): [0 .. 15] adjacent equal keys per frame (the same voxel in two frames is no duplicate), [16 .. 31] rows per frame,
+ * [32] bit 0 = a coordinate outside [0, 2^20), bit 1 = a frame index outside 0 .. frames - 1. */
+int64_t pcgc_raht_keys_batch_workspace_bytes(int64_t n);
+int pcgc_raht_keys_batch(const int32_t* coords, int64_t n, int frames, uint64_t* keys, int32_t* perm, int32_t* status, void* workspace,
+                         size_t workspace_bytes, void* stream);
+/* as pcgc_raht_tree.  order [n-1]: the n - frames merges in coding order (frame, then d descending, then gap ascending), then the frame
+ * boundaries; cross_order [n-1]: the merges whose range crosses a multiple of pcgc_raht_tile_leaves() by d descending, then the other
+ * merges by d descending, then the boundaries.  offsets [(frames + 1) x 65] (dev): bucket [65] of every frame, counted from the frame's own
+ * first position of the order, then cross [65] of the batch. */
+int64_t pcgc_raht_tree_batch_workspace_bytes(int64_t n);
+int pcgc_raht_tree_batch(const uint64_t* keys, int64_t n, int frames, uint8_t* d, int32_t* lo, int32_t* hi, int32_t* left, int32_t* right,
+                         int32_t* order, int32_t* cross_order, int32_t* offsets, void* workspace, size_t workspace_bytes, void* stream);
+/* as pcgc_raht_forward; row start_b of val is frame b's DC.  bit_off [130] on the HOST: the 65 offsets into cross_order of the crossing
+ * merges (= cross), then those of the others (they start at cross[64]); form 0 launches both runs of a split bit.  cross_off [65] (dev):
+ * the last row of pcgc_raht_tree_batch's offsets. */
+int pcgc_raht_forward_batch(const uint8_t* rgb, const int32_t* perm, int64_t n, const uint8_t* d, const int32_t* lo, const int32_t* hi,
+                            const int32_t* cross_order, const int32_t* bit_off, const int32_t* cross_off, int form, int32_t* val, int32_t* H,
+                            void* stream);
+/* as pcgc_raht_inverse; dc [frames,3] and starts [frames] (= start_b) on the device. */
+int pcgc_raht_inverse_batch(const int32_t* Hhat, const int32_t* dc, const int32_t* starts, int frames, const int32_t* perm, int64_t n,
+                            const uint8_t* d, const int32_t* lo, const int32_t* hi, const int32_t* cross_order, const int32_t* bit_off,
+                            const int32_t* cross_off, int form, int32_t* val, uint8_t* rgb, void* stream);
+/* as pcgc_raht_quantize over the 3 (n - frames) tokens of the batch's coding order: frame b's tokens, contexts and escapes are consecutive,
+ * frame by frame.  q_luma, q_chroma [frames] on the HOST.  hist [frames,48,64] (dev); n_escapes [1] (dev) counts all frames, frame b's
+ * share is the sum of hist[b][.][63]. */
+int64_t pcgc_raht_quantize_batch_workspace_bytes(int64_t n, int frames);
+int pcgc_raht_quantize_batch(const int32_t* H, int64_t n, int frames, const uint64_t* keys, const uint8_t* d, const int32_t* lo, const int32_t* hi,
+                             const int32_t* order, const int32_t* q_luma, const int32_t* q_chroma, int16_t* tokens, uint16_t* ctx,
+                             uint16_t* escapes, int32_t* n_escapes, int32_t* hist, void* workspace, size_t workspace_bytes, void* stream);
+/* as pcgc_raht_dequantize; escapes: the frames' lists one after the other, n_escapes in all.  n_escape_tokens [17] (dev): the tokens that
+ * are 63 per frame [0 .. 15], then of the batch; the caller refuses a frame whose escape list has another length. */
+int64_t pcgc_raht_dequantize_batch_workspace_bytes(int64_t n, int frames);
+int pcgc_raht_dequantize_batch(const int16_t* tokens, const uint16_t* escapes, int64_t n_escapes, int64_t n, int frames, const uint64_t* keys,
+                               const int32_t* lo, const int32_t* hi, const int32_t* order, const int32_t* q_luma, const int32_t* q_chroma,
+                               int32_t* Hhat, int32_t* n_escape_tokens, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Colour codec, `_A.bin` version 2 (csrc/attribute_rans.hip; the definition is tests/attr_rans_reference.py): the tokens
  *      of pcgc_raht_quantize coded ON THE DEVICE by interleaved rANS, the coder of `_O.bin` version 2 above with a 64-ary token in place of
  *      a bit.  One wave per chunk of 64 S tokens; 64 independent states, one per lane, share one stream of 32-bit words.  The payload,
@@ -654,6 +695,25 @@ int pcgc_attr_rans_encode(const uint16_t* table /*[dev 48,65]*/, const uint16_t*
 int pcgc_attr_rans_decode(const uint16_t* table /*[dev 48,65]*/, const int32_t* bucket /*[dev 65]*/, int64_t n, const uint8_t* payload,
                           int64_t payload_bytes, int steps, int16_t* tokens /*[dev n]*/, int64_t* host2, void* workspace,
                           size_t workspace_bytes, void* stream);
+/* A batch of 1 .. 16 frames in ONE launch sequence.  Chunks never straddle frames: frame f holds tokens [tok[f], tok[f+1])
+ * of the batch's coding order (tok [frames + 1] on the HOST, ascending multiples of 3 from 0, tok[frames] = n) in K_f = ceil(n_f / (64
+ * steps[f])) chunks (steps [frames] on the HOST), and its payload, in the layout above with its own S | K | states | W_k | words, stands at
+ * byte pay[f] (a multiple of 8, HOST) of `payload`.  A frame without tokens has no chunk and an empty payload.  tables [dev frames,48,65];
+ * a workgroup serves chunks of one frame and loads that frame's table.  workspace: pcgc_attr_rans_batch_workspace_bytes(n, K) device
+ * bytes, K = the chunks of all frames; an entry given less refuses with -2 before anything is launched, as does a batch without tokens. */
+int64_t pcgc_attr_rans_batch_workspace_bytes(int64_t n, int64_t chunks);
+/* pay [frames + 1]: frame f has room for 8 + 516 K_f + 4 n_f bytes between pay[f] and pay[f + 1].  host [2 frames] = every frame's payload
+ * length in bytes, then every frame's tokens that could not be coded: ONE small synchronising copy for the batch. */
+int pcgc_attr_rans_encode_batch(const uint16_t* tables, const uint16_t* ctx, const int16_t* tokens, int frames, const int64_t* tok,
+                                const int32_t* steps, uint8_t* payload, const int64_t* pay, int64_t* host, void* workspace,
+                                size_t workspace_bytes, void* stream);
+/* bucket [dev frames,65]: the first `frames` rows of pcgc_raht_tree_batch's offsets.  steps[f] = 0: frame f is not decoded here (its file
+ * is version 1, or it has no token) and its slice of `tokens` is left alone.  pay_bytes [frames] (HOST): the length of each payload, whose
+ * head the caller has checked as for pcgc_attr_rans_decode.  host [2 frames] = every frame's tokens that are 63, then every frame's
+ * unsound chunks: ONE small synchronising copy for the batch. */
+int pcgc_attr_rans_decode_batch(const uint16_t* tables, const int32_t* bucket, int frames, const int64_t* tok, const int32_t* steps,
+                                const uint8_t* payload, const int64_t* pay, const int64_t* pay_bytes, int16_t* tokens, int64_t* host,
+                                void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Estimated surface normals of a voxelised cloud (csrc/normals.hip; nothing in the reference: its D2 figures assume clouds whose normals
  *      another tool estimated).  Per row at voxel p: the neighbourhood is every DISTINCT voxel q of the row's batch with |q - p|^2 <= r2 (p

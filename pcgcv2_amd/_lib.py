@@ -141,6 +141,19 @@ SIGNATURES = {
     'pcgc_raht_quantize': (ci, [vp, i64, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
     'pcgc_raht_dequantize_workspace_bytes': (sz, [i64]),
     'pcgc_raht_dequantize': (ci, [vp, vp, i64, i64, vp, vp, vp, ci, ci, vp, vp, vp, sz, vp]),
+    'pcgc_raht_keys_batch_workspace_bytes': (i64, [i64]),
+    'pcgc_raht_keys_batch': (ci, [vp, i64, ci, vp, vp, vp, vp, sz, vp]),
+    'pcgc_raht_tree_batch_workspace_bytes': (i64, [i64]),
+    'pcgc_raht_tree_batch': (ci, [vp, i64, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'pcgc_raht_forward_batch': (ci, [vp, vp, i64, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]),
+    'pcgc_raht_inverse_batch': (ci, [vp, vp, vp, ci, vp, i64, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]),
+    'pcgc_raht_quantize_batch_workspace_bytes': (i64, [i64, ci]),
+    'pcgc_raht_quantize_batch': (ci, [vp, i64, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'pcgc_raht_dequantize_batch_workspace_bytes': (i64, [i64, ci]),
+    'pcgc_raht_dequantize_batch': (ci, [vp, vp, i64, i64, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'pcgc_attr_rans_batch_workspace_bytes': (i64, [i64, i64]),
+    'pcgc_attr_rans_encode_batch': (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'pcgc_attr_rans_decode_batch': (ci, [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     'pcgc_normals_ball_masks': (i64, [i32, vp]),
     'pcgc_normals_workspace_bytes': (sz, [i64]),
     'pcgc_normals_estimate': (ci, [vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, i32, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]),

@@ -21,7 +21,10 @@ The tables are semi-static, per stream: frequencies out of 65536 from the stream
 field and the payload alone; a decoder reads either, whatever coder it was made with.  In version 2 the tokens and their contexts never
 cross the bus: the encoder copies down the histogram, the DC and the escapes, the decoder copies up the tables, the payload and the escapes.
 
-    python -m pcgcv2_amd.attributes --filedir CLOUD.ply --qstep Q [--qstep_chroma Qc] [--outdir DIR] [--attribute_coder device [--chunk_steps S]]
+AttributeCoder.encode_batch / decode_batch code up to 16 frames in one pass over the device: the same files, the same colours.
+
+    python -m pcgcv2_amd.attributes --filedir CLOUD.ply [MORE.ply ...] --qstep Q [--qstep_chroma Qc] [--outdir DIR]
+                                    [--attribute_coder device [--chunk_steps S]]        (several files: one batch)
 """
 import os
 import struct
@@ -168,7 +171,8 @@ class AttributeCoder():
     int32 [N,4] device rows (0, x, y, z) of distinct voxels (or [N,3] rows (x, y, z)); a batch, duplicates or coordinates outside
     [0, 2^20) are a ValueError.  form: ops.RAHT_FORMS (None: ops.RAHT_FORM); the bytes and colours do not depend on it.
     attribute_coder: 'host' writes version 1, 'device' version 2 in chunks of 64 x chunk_steps tokens (0: one chunk); decode reads either
-    version whatever these two say."""
+    version whatever these two say.  encode_batch / decode_batch take rows (b, x, y, z) of up to 16 frames through the device once and
+    write / read every frame's own file: the bytes and colours of encode / decode on that frame alone."""
 
     def __init__(self, filename, form=None, attribute_coder='host', chunk_steps=CHUNK_STEPS):
         if attribute_coder not in CODERS:
@@ -276,6 +280,141 @@ class AttributeCoder():
             self._tick('inverse', t, dev)
         return rgb
 
+    # ---- a batch of frames in one pass: the files and colours of frame-by-frame coding, the device work done once
+    @staticmethod
+    def _batch_args(coords, postfixes, qstep=0, qstep_chroma=None):
+        """everything about a batch that can be refused without the device -> (B, q_luma [B], q_chroma [B])"""
+        if isinstance(postfixes, str) or postfixes is None:
+            raise ValueError('postfixes: a list of one distinct string per frame')
+        postfixes = list(postfixes)
+        B = len(postfixes)
+        if not 1 <= B <= ops.RAHT_MAX_FRAMES:
+            raise ValueError(f'{B} frames: a batch holds 1 .. {ops.RAHT_MAX_FRAMES} (code larger sets in several batches)')
+        if len(set(postfixes)) != B or not all(isinstance(p, str) for p in postfixes):
+            raise ValueError(f'postfixes {postfixes}: one distinct string per frame')
+
+        def steps(q, what):
+            q = [q] * B if isinstance(q, (int, np.integer)) and not isinstance(q, bool) else list(q) if hasattr(q, '__len__') else None
+            if q is None or len(q) != B:
+                raise ValueError(f'{what}: an integer or a sequence of {B}, one per frame')
+            if not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 0 <= v <= 255 for v in q):
+                raise ValueError(f'{what} {q}: integers in 0 .. 255')
+            return [int(v) for v in q]
+        ql = steps(qstep, 'qstep')
+        qc = ql if qstep_chroma is None else steps(qstep_chroma, 'qstep_chroma')
+        if torch.is_tensor(coords) and coords.dim() == 2 and coords.shape[0] > ops.RAHT_MAX_POINTS:
+            raise ValueError(f'{coords.shape[0]} rows: a batch holds 2^24 at most')
+        if torch.is_tensor(coords) and (coords.dim() != 2 or coords.shape[1] != 4):
+            raise ValueError(f'a batch takes coordinates [N,4] rows (frame, x, y, z), got {tuple(coords.shape)}')
+        return B, ql, qc
+
+    def _batch_tree(self, coords, B, tree):
+        if tree is None:
+            tree = ops.raht_tree_batch(coords, B, times=self.times)
+        elif tree.n != coords.shape[0] or getattr(tree, 'frames', None) != B:
+            raise ValueError(f'AttributeCoder: a tree of {tree.n} leaves for {coords.shape[0]} rows in {B} frames')
+        return tree
+
+    @torch.no_grad()
+    def encode_batch(self, coords, rgb, qstep, qstep_chroma=None, postfixes=('',), tree=None):
+        """coords int32 [N,4] device rows (b, x, y, z), b = 0 .. B - 1 in any order, B = len(postfixes) = 1 .. 16 frames of at least one
+        row each; rgb uint8 [N,3] in the same row order; qstep, qstep_chroma: an int or B ints -> writes `filename + postfixes[b] + '_A.bin'`
+        for every b, byte for byte what encode writes for frame b alone; -> B records {bits_A, tokens, escapes, payload_bytes}.  One key
+        build and sort, one tree build, one transform, one quantiser pass and (attribute_coder='device') one coder launch sequence for the
+        batch; 'host' brings tokens and contexts down once and codes each frame's slice on coder._batch_pool.  tree:
+        ops.raht_tree_batch(coords, B) when the caller holds it already."""
+        from .coder import _batch_pool
+        B, ql, qc = self._batch_args(coords, postfixes, qstep, qstep_chroma)
+        coords = self._coords(coords)
+        dev = coords.device
+        with torch.cuda.device(dev):
+            tree = self._batch_tree(coords, B, tree)
+            t = self._tick(None, 0.0, dev)
+            H, dc = ops.raht_forward_batch(tree, rgb, form=self.form)
+            t = self._tick('forward', t, dev)
+            tokens, ctx, esc, hist = ops.raht_quantize_batch(tree, H, ql, qc)
+            t = self._tick('quantise', t, dev)
+            device = self.attribute_coder == 'device'
+            tok = tree.tok
+            if not device:
+                tokens_h, ctx_h = tokens.cpu().numpy(), ctx.cpu().numpy().view(np.uint16)
+            hist_h, dc_h = hist.cpu().numpy(), dc.cpu().tolist()
+            n_esc = hist_h[:, :, ESCAPE].sum(1).astype(np.int64)           # frame b's escapes follow those of the frames before it
+            esc_at = np.concatenate([[0], np.cumsum(n_esc)])
+            esc_h = esc[:int(esc_at[-1])].cpu().numpy().view(np.uint16)
+            t = self._tick('copies', t, dev)
+            made = [frequency_rows(hist_h[b]) for b in range(B)]
+            if device:                            # the tokens and contexts stay where pcgc_raht_quantize_batch wrote them
+                payloads = ops.attr_rans_encode_batch(np.stack([m[1] for m in made]), ctx, tokens, tok, self.chunk_steps)
+                t = self._tick('device coder', t, dev)
+            else:
+                def one(b):                       # a frame's slice on a host thread (the native coder releases the GIL)
+                    mine = slice(int(tok[b]), int(tok[b + 1]))
+                    return ops.rc_encode_ctx(made[b][1], ctx_h[mine], tokens_h[mine]) if tok[b + 1] > tok[b] else b''
+                payloads = list(_batch_pool().map(one, range(B)))
+            records = []
+            for b in range(B):
+                (rows, table), n_tok, e = made[b], int(tok[b + 1] - tok[b]), esc_h[esc_at[b]:esc_at[b + 1]]
+                blob = _HEAD.pack(MAGIC, CODERS[self.attribute_coder], n_tok // 3 + 1, ql[b], qc[b], dc_h[b][0], dc_h[b][1], dc_h[b][2], len(rows))
+                blob += b''.join(struct.pack('<H', c) + table[c, 1:TOKENS].astype('<u2').tobytes() for c in rows)
+                blob += _SIZES.pack(n_tok, len(payloads[b]), e.size) + payloads[b] + _pack_escapes(e)
+                blob += struct.pack('<I', ops.crc32(blob))
+                _dump(self.filename + postfixes[b] + SUFFIX, blob)
+                records.append({'bits_A': 8 * len(blob), 'tokens': n_tok, 'escapes': int(e.size), 'payload_bytes': len(payloads[b])})
+            self._tick('host coder', t)
+        return records
+
+    @torch.no_grad()
+    def decode_batch(self, coords, postfixes=('',), tree=None):
+        """the colours of `filename + postfixes[b] + '_A.bin'`, b = 0 .. B - 1, for the rows (b, x, y, z) of coords -> uint8 [N,3] device
+        tensor in the row order of coords: per frame what decode returns.  Every item is read in the version its file has (version-1
+        payloads on the host threads of coder._batch_pool, version-2 payloads in one launch sequence on the device); the host checks of
+        all items run before anything is launched.  PcgcError naming the file that is cut, extended, damaged or not made for its frame."""
+        from .coder import _batch_pool
+        B, _, _ = self._batch_args(coords, postfixes)
+        coords = self._coords(coords)
+        dev = coords.device
+        paths = [self.filename + p + SUFFIX for p in postfixes]
+        with torch.cuda.device(dev):
+            tree = self._batch_tree(coords, B, tree)
+            t = self._tick(None, 0.0, dev)
+            tok, rows = tree.tok, np.diff(tree.starts)
+            items = [read_container(paths[b], int(rows[b]), tree.bucket[b]) for b in range(B)]
+            for b in range(B):
+                if items[b][0] == VERSION_DEVICE:
+                    try:
+                        ops.attr_rans_layout(items[b][5], int(tok[b + 1] - tok[b]))
+                    except PcgcError as e:
+                        raise PcgcError(f'{paths[b]}: {e}') from None
+            esc = np.concatenate([it[6] for it in items]) if B else np.zeros(0, np.uint16)
+            n_esc = [int(it[6].size) for it in items]
+            host = [b for b in range(B) if items[b][0] == VERSION]
+            tokens_d = None
+            if host:                              # version-1 items: decoded on the host, their slices go up in one copy
+                tokens_h = np.zeros(int(tok[-1]), np.int16)
+                for b, got in zip(host, _batch_pool().map(lambda b: _host_tokens(paths[b], items[b][4], tree.bucket[b], items[b][5], items[b][6]), host)):
+                    tokens_h[tok[b]:tok[b + 1]] = got
+                tokens_d = torch.from_numpy(tokens_h).to(dev)
+            t = self._tick('host coder', t)
+            if len(host) < B:                     # version-2 items: decoded where they are used, all of them in one launch sequence
+                tokens_d, n_escape = ops.attr_rans_decode_batch(np.stack([it[4] for it in items]), tree,
+                                                                [it[5] if it[0] == VERSION_DEVICE else None for it in items], tokens=tokens_d,
+                                                                names=paths)
+                for b in range(B):
+                    if items[b][0] == VERSION_DEVICE and int(n_escape[b]) != n_esc[b]:
+                        raise PcgcError(f'{paths[b]}: {int(n_escape[b])} escape tokens but {n_esc[b]} escapes')
+                t = self._tick('device coder', t, dev)
+            esc_d = torch.from_numpy(esc.view(np.int16).copy()).to(dev)
+            t = self._tick('copies', t, dev)
+            try:
+                Hhat = ops.raht_dequantize_batch(tree, tokens_d, esc_d, n_esc, [it[1] for it in items], [it[2] for it in items])
+            except PcgcError as e:
+                raise PcgcError(f'{self.filename}{list(postfixes)}{SUFFIX}: {e}') from None
+            t = self._tick('dequantise', t, dev)
+            rgb = ops.raht_inverse_batch(tree, Hhat, [it[3] for it in items], form=self.form)
+            self._tick('inverse', t, dev)
+        return rgb
+
 
 def attribute_bits(prefix, postfix=''):
     """bits of `_A.bin` of one coded cloud"""
@@ -310,10 +449,49 @@ def run(filedir, outdir, qstep, qstep_chroma=None, attribute_coder='host', chunk
     return record, metric
 
 
+def run_batch(filedirs, outdir, qstep, qstep_chroma=None, attribute_coder='host', chunk_steps=CHUNK_STEPS):
+    """several clouds collated into one batch and coded with encode_batch / decode_batch: per file the figures and the `_dec.ply` of run"""
+    from .coder import device, _Stopwatch
+    from .data_utils import read_ply_ascii_with_colours, write_ply_ascii_geo_rgb
+    from .pc_error import colour_psnr_device, lattice_coords
+    from .sparse import require_gpu
+    require_gpu(device)
+    names = [os.path.split(f)[-1].split('.')[0] for f in filedirs]
+    if len(set(names)) != len(names):
+        raise ValueError(f'{names}: the files of a batch need distinct names, they name the outputs')
+    clouds = [read_ply_ascii_with_colours(f) for f in filedirs]
+    for f, (_, rgb) in zip(filedirs, clouds):
+        if rgb is None:
+            raise ValueError(f'{f} has no colours (red green blue)')
+    os.makedirs(outdir, exist_ok=True)
+    prefix = os.path.join(outdir, '')
+    parts = [lattice_coords(xyz, device, batch=b) for b, (xyz, _) in enumerate(clouds)]
+    a, ca = torch.cat(parts), torch.from_numpy(np.concatenate([rgb for _, rgb in clouds])).to(device)
+    coder = AttributeCoder(prefix, attribute_coder=attribute_coder, chunk_steps=chunk_steps)
+    with _Stopwatch('Enc Time'):
+        records = coder.encode_batch(a, ca, qstep, qstep_chroma, postfixes=names)
+    with _Stopwatch('Dec Time'):
+        cb = coder.decode_batch(a, postfixes=names)
+    metrics, at = [], 0
+    for b, (xyz, _) in enumerate(clouds):
+        rows = slice(at, at + len(xyz))
+        at += len(xyz)
+        print(prefix + names[b])
+        print(f'{SUFFIX}:\t {records[b]["bits_A"]} bits\t {round(records[b]["bits_A"] / len(xyz), 3)} bpp')
+        single = torch.cat([torch.zeros_like(a[rows, :1]), a[rows, 1:]], 1)
+        metric = colour_psnr_device(single, ca[rows], single, cb[rows])
+        print('Colour PSNR (Y):\t', metric['c[0],PSNRF'])
+        print('Colour PSNR (U, V):\t', metric['c[1],PSNRF'], metric['c[2],PSNRF'])
+        write_ply_ascii_geo_rgb(prefix + names[b] + '_dec.ply', xyz, cb[rows].cpu().numpy())
+        metrics.append(metric)
+    return records, metrics
+
+
 def main(argv=None):
     import argparse
     p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
-    p.add_argument("--filedir", required=True, help="an ASCII PLY of distinct voxels with red green blue")
+    p.add_argument("--filedir", required=True, nargs='+',
+                   help="an ASCII PLY of distinct voxels with red green blue; several (up to 16): collated and coded as one batch")
     p.add_argument("--qstep", type=int, required=True, help="quantiser step of the luma channel, 0 .. 255 (0: lossless)")
     p.add_argument("--qstep_chroma", type=int, default=None, help="quantiser step of Co and Cg (default: --qstep)")
     p.add_argument("--outdir", default='./output')
@@ -321,7 +499,10 @@ def main(argv=None):
                    help="host: the payload coded by the host range coder (_A.bin version 1); device: interleaved rANS on the GPU (version 2)")
     p.add_argument("--chunk_steps", type=int, default=CHUNK_STEPS, help="device coder: steps per chunk of 64 lanes (0: one chunk)")
     args = p.parse_args(argv)
-    run(args.filedir, args.outdir, args.qstep, args.qstep_chroma, args.attribute_coder, args.chunk_steps)
+    if len(args.filedir) == 1:
+        run(args.filedir[0], args.outdir, args.qstep, args.qstep_chroma, args.attribute_coder, args.chunk_steps)
+    else:
+        run_batch(args.filedir, args.outdir, args.qstep, args.qstep_chroma, args.attribute_coder, args.chunk_steps)
 
 
 if __name__ == '__main__':

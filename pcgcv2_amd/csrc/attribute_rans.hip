@@ -20,7 +20,11 @@
 //            memory and the token is in 0 .. 63 whatever the table says.  Words are staged through a ring in LDS as in occupancy_rans.hip.
 //            The contexts come from k_attr_rans_ctx, which derives them from the tree's bucket offsets: they are never uploaded.
 //
+// A batch of frames (pcgc_attr_rans_*_batch) is one launch of the chunks of all frames: the chunk bodies below are shared, a
+// workgroup serves one frame's chunk with that frame's table, and every frame's payload is packed on its own.
+//
 // No workgroup reads what another wrote in the same launch.  All integer arithmetic: the bytes are a function of the input alone.
+#include <cstring>
 #include "pcgc_common.h"
 
 constexpr int AR_LANES = 64;
@@ -64,18 +68,12 @@ __device__ static inline void ar_divmod(uint64_t x, uint32_t f, uint64_t& q, uin
 static inline int64_t ar_chunks(int64_t n, int steps) { return (n + (int64_t)AR_LANES * steps - 1) / ((int64_t)AR_LANES * steps); }
 
 // ---- encoder ---------------------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(AR_LANES) k_attr_rans_encode(const uint16_t* __restrict__ table, const uint16_t* __restrict__ ctx,
-                                                               const int16_t* __restrict__ tokens, int64_t n, int S, uint32_t* __restrict__ scratch,
-                                                               unsigned long long* __restrict__ states, uint32_t* __restrict__ wcount,
-                                                               unsigned long long* __restrict__ refused) {
-    __shared__ __attribute__((aligned(16))) uint32_t sh[AR_CONTEXTS * AR_ROW];
-    ar_load_table(sh, table);
+// one chunk of `rows` tokens by one wave: sh = the LDS rows of its table; out: rows words of scratch, of which [top, rows) are written;
+// states: the chunk's 64, wcount: its word count, refused: the counter of the tokens that cannot be coded
+__device__ __forceinline__ void ar_encode_chunk(const uint32_t* sh, const uint16_t* __restrict__ in_c, const int16_t* __restrict__ in_t, int rows,
+                                                uint32_t* __restrict__ out, unsigned long long* __restrict__ states, uint32_t* __restrict__ wcount,
+                                                unsigned long long* __restrict__ refused) {
     const int lane = threadIdx.x;
-    const int64_t k = blockIdx.x, base = k * AR_LANES * S;
-    const int rows = (int)(n - base < (int64_t)AR_LANES * S ? n - base : (int64_t)AR_LANES * S);
-    const uint16_t* __restrict__ in_c = ctx + base;
-    const int16_t* __restrict__ in_t = tokens + base;
-    uint32_t* __restrict__ out = scratch + base;              // rows words: [top, rows) are written
     const int steps = (rows + AR_LANES - 1) / AR_LANES;       // steps that hold a token at all
     int top = rows;
     uint64_t x = AR_L;
@@ -120,18 +118,58 @@ __global__ void __launch_bounds__(AR_LANES) k_attr_rans_encode(const uint16_t* _
         for (int i = 0; i < AR_BATCH; ++i) cur[i] = nxt[i];
     }
 #undef AR_FETCH
-    states[k * AR_LANES + lane] = x;
-    if (lane == 0) wcount[k] = (uint32_t)(rows - top);
+    states[lane] = x;
+    if (lane == 0) *wcount = (uint32_t)(rows - top);
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) bad += __shfl_xor(bad, d, 64);
     if (lane == 0 && bad) atomicAdd(refused, (unsigned long long)bad);           // (integer atomic: the sum does not depend on the order)
 }
+__global__ void __launch_bounds__(AR_LANES) k_attr_rans_encode(const uint16_t* __restrict__ table, const uint16_t* __restrict__ ctx,
+                                                               const int16_t* __restrict__ tokens, int64_t n, int S, uint32_t* __restrict__ scratch,
+                                                               unsigned long long* __restrict__ states, uint32_t* __restrict__ wcount,
+                                                               unsigned long long* __restrict__ refused) {
+    __shared__ __attribute__((aligned(16))) uint32_t sh[AR_CONTEXTS * AR_ROW];
+    ar_load_table(sh, table);
+    const int64_t k = blockIdx.x, base = k * AR_LANES * S;
+    const int rows = (int)(n - base < (int64_t)AR_LANES * S ? n - base : (int64_t)AR_LANES * S);
+    ar_encode_chunk(sh, ctx + base, tokens + base, rows, scratch + base, states + k * AR_LANES, wcount + k, refused);
+}
+
+// A batch of frames in ONE launch sequence (pcgc_attr_rans_*_batch): chunks never straddle frames, so a workgroup serves one frame and loads
+// that frame's table.  The table below travels by value; chunk k of the launch belongs to the last frame f with chunk[f] <= k.
+constexpr int AR_MAX_FRAMES = 16;
+struct ArFrames {
+    long long tok[AR_MAX_FRAMES + 1];          // first token of the frame in the batch's coding order; tok[frames] = all tokens
+    long long pay[AR_MAX_FRAMES];              // byte offset of the frame's payload in the payload buffer, a multiple of 8
+    long long words[AR_MAX_FRAMES];            // decoder: 32-bit words the frame's payload holds behind its tables
+    int chunk[AR_MAX_FRAMES + 1];              // first chunk of the frame; chunk[frames] = all chunks (a frame may have none)
+    int steps[AR_MAX_FRAMES];
+    int frames;
+};
+__device__ static inline int ar_frame_of(const ArFrames& fr, int64_t k) {
+    int f = 0;
+    for (int b = 1; b < AR_MAX_FRAMES; ++b) f += (b < fr.frames && (int64_t)fr.chunk[b] <= k) ? 1 : 0;     // (chunk[] ascends)
+    return f;
+}
+__global__ void __launch_bounds__(AR_LANES) k_attr_rans_encode_batch(const uint16_t* __restrict__ tables, const uint16_t* __restrict__ ctx,
+                                                                     const int16_t* __restrict__ tokens, ArFrames fr, uint32_t* __restrict__ scratch,
+                                                                     uint8_t* __restrict__ payload, unsigned long long* __restrict__ refused) {
+    __shared__ __attribute__((aligned(16))) uint32_t sh[AR_CONTEXTS * AR_ROW];
+    const int f = ar_frame_of(fr, blockIdx.x);
+    ar_load_table(sh, tables + (size_t)f * AR_CONTEXTS * (AR_TOKENS + 1));
+    const int S = fr.steps[f];
+    const int64_t k = (int64_t)blockIdx.x - fr.chunk[f], K = fr.chunk[f + 1] - fr.chunk[f], n = fr.tok[f + 1] - fr.tok[f];
+    const int64_t base = k * AR_LANES * S;
+    const int rows = (int)(n - base < (int64_t)AR_LANES * S ? n - base : (int64_t)AR_LANES * S);
+    uint8_t* mine = payload + fr.pay[f];
+    ar_encode_chunk(sh, ctx + fr.tok[f] + base, tokens + fr.tok[f] + base, rows, scratch + fr.tok[f] + base,
+                    (unsigned long long*)(mine + 8) + k * AR_LANES, (uint32_t*)(mine + 8 + 512 * K) + k, refused + f);
+}
 
 // exclusive scan of the chunks' word counts (one block; thread t owns a run of consecutive chunks) -> offs [K] (saturating: counts a decoder
 // reads are not to be trusted), slot[0] = their sum.  Encoder side: also the payload's head.
-__global__ void __launch_bounds__(AR_SCAN_BLOCK) k_attr_rans_offsets(const uint32_t* __restrict__ wcount, int64_t K, uint32_t* __restrict__ offs,
-                                                                     long long* __restrict__ slot, uint32_t* __restrict__ head, uint32_t S) {
-    __shared__ unsigned long long part[AR_SCAN_BLOCK];
+__device__ __forceinline__ void ar_offsets(unsigned long long* part, const uint32_t* __restrict__ wcount, int64_t K, uint32_t* __restrict__ offs,
+                                           long long* __restrict__ slot, uint32_t* __restrict__ head, uint32_t S) {
     const int64_t per = (K + AR_SCAN_BLOCK - 1) / AR_SCAN_BLOCK;
     const int64_t lo = (int64_t)threadIdx.x * per < K ? (int64_t)threadIdx.x * per : K, hi = lo + per < K ? lo + per : K;
     unsigned long long s = 0;
@@ -148,6 +186,23 @@ __global__ void __launch_bounds__(AR_SCAN_BLOCK) k_attr_rans_offsets(const uint3
     unsigned long long run = part[threadIdx.x];
     for (int64_t i = lo; i < hi; ++i) { offs[i] = run < 0xffffffffull ? (uint32_t)run : 0xffffffffu; run += wcount[i]; }
 }
+__global__ void __launch_bounds__(AR_SCAN_BLOCK) k_attr_rans_offsets(const uint32_t* __restrict__ wcount, int64_t K, uint32_t* __restrict__ offs,
+                                                                     long long* __restrict__ slot, uint32_t* __restrict__ head, uint32_t S) {
+    __shared__ unsigned long long part[AR_SCAN_BLOCK];
+    ar_offsets(part, wcount, K, offs, slot, head, S);
+}
+// block f: frame f's chunks -> offs [chunk[f] ..) counted from the frame's own first word, slot[f] = the frame's words; a frame without
+// chunks has no head (its payload is empty)
+__global__ void __launch_bounds__(AR_SCAN_BLOCK) k_attr_rans_offsets_batch(ArFrames fr, uint8_t* payload, uint32_t* __restrict__ offs,
+                                                                           long long* __restrict__ slot, int with_head) {
+    __shared__ unsigned long long part[AR_SCAN_BLOCK];
+    const int f = blockIdx.x;
+    const int64_t K = fr.chunk[f + 1] - fr.chunk[f];
+    if (K <= 0) { if (threadIdx.x == 0) slot[f] = 0; return; }      // (uniform)
+    uint8_t* mine = payload + fr.pay[f];
+    ar_offsets(part, (const uint32_t*)(mine + 8 + 512 * K), K, offs + fr.chunk[f], slot + f, with_head ? (uint32_t*)mine : (uint32_t*)nullptr,
+               (uint32_t)fr.steps[f]);
+}
 
 // chunk k's words, from the end of its scratch to their place in the payload
 __global__ void __launch_bounds__(AR_SCAN_BLOCK) k_attr_rans_compact(const uint32_t* __restrict__ scratch, int64_t n, int S, const uint32_t* __restrict__ wcount,
@@ -157,6 +212,19 @@ __global__ void __launch_bounds__(AR_SCAN_BLOCK) k_attr_rans_compact(const uint3
     const uint32_t W = wcount[k];                             // <= rows: the encoder wrote it
     const uint32_t* __restrict__ src = scratch + base + rows - W;
     uint32_t* __restrict__ dst = words + offs[k];
+    for (uint32_t i = threadIdx.x; i < W; i += AR_SCAN_BLOCK) dst[i] = src[i];
+}
+__global__ void __launch_bounds__(AR_SCAN_BLOCK) k_attr_rans_compact_batch(const uint32_t* __restrict__ scratch, ArFrames fr, const uint32_t* __restrict__ offs,
+                                                                           uint8_t* __restrict__ payload) {
+    const int f = ar_frame_of(fr, blockIdx.x);
+    const int S = fr.steps[f];
+    const int64_t k = (int64_t)blockIdx.x - fr.chunk[f], K = fr.chunk[f + 1] - fr.chunk[f], n = fr.tok[f + 1] - fr.tok[f];
+    const int64_t base = k * AR_LANES * S;
+    const int64_t rows = n - base < (int64_t)AR_LANES * S ? n - base : (int64_t)AR_LANES * S;
+    const uint32_t* wcount = (const uint32_t*)(payload + fr.pay[f] + 8 + 512 * K);
+    const uint32_t W = wcount[k];                             // <= rows: the encoder wrote it
+    const uint32_t* __restrict__ src = scratch + fr.tok[f] + base + rows - W;
+    uint32_t* __restrict__ dst = (uint32_t*)(wcount + K) + offs[blockIdx.x];
     for (uint32_t i = threadIdx.x; i < W; i += AR_SCAN_BLOCK) dst[i] = src[i];
 }
 
@@ -179,26 +247,18 @@ __global__ void __launch_bounds__(AR_SCAN_BLOCK) k_attr_rans_ctx(const int32_t* 
     if (3 * p + 2 < n) ctx[3 * p + 2] = (uint16_t)(32 + level);
 }
 
-__global__ void __launch_bounds__(AR_LANES) k_attr_rans_decode(const uint16_t* __restrict__ table, const uint16_t* __restrict__ ctx, int64_t n, int S,
-                                                               const unsigned long long* __restrict__ states, const uint32_t* __restrict__ wcount,
-                                                               const uint32_t* __restrict__ offs, const uint32_t* __restrict__ words,
-                                                               int64_t words_total, int16_t* __restrict__ tokens,
-                                                               unsigned long long* __restrict__ result /*[0] tokens that are 63, [1] unsound chunks*/) {
-    __shared__ __attribute__((aligned(16))) uint32_t sh[AR_CONTEXTS * AR_ROW];
-    __shared__ uint32_t ring[AR_RING];
-    ar_load_table(sh, table);
+// one chunk of `rows` tokens by one wave: sh = the LDS rows of its table, ring: AR_RING words of LDS; in / out: the chunk's contexts and
+// tokens; states: its 64; W, off: its word count and where its words start among the words_total of `words`
+__device__ __forceinline__ void ar_decode_chunk(const uint32_t* sh, uint32_t* ring, const uint16_t* __restrict__ in, int rows,
+                                                const unsigned long long* __restrict__ states, uint32_t W, int64_t off,
+                                                const uint32_t* __restrict__ words, int64_t words_total, int16_t* __restrict__ out,
+                                                unsigned long long* __restrict__ result /*[0] tokens that are 63, [1] unsound chunks*/) {
     const int lane = threadIdx.x;
-    const int64_t k = blockIdx.x, base = k * AR_LANES * S;
-    const int rows = (int)(n - base < (int64_t)AR_LANES * S ? n - base : (int64_t)AR_LANES * S);
     const int steps = (rows + AR_LANES - 1) / AR_LANES;
-    const uint16_t* __restrict__ in = ctx + base;
-    int16_t* __restrict__ out = tokens + base;
-    const uint32_t W = wcount[k];
-    const int64_t off = (int64_t)offs[k];
     // the words this chunk may read: [0, avail) of src, inside both its own count and the payload
     const uint32_t avail = off >= words_total ? 0u : (uint32_t)((int64_t)W < words_total - off ? (int64_t)W : words_total - off);
     const uint32_t* __restrict__ src = words + (off < words_total ? off : 0);
-    uint64_t x = states[k * AR_LANES + lane];
+    uint64_t x = states[lane];
     bool bad = x < AR_L || x >= AR_STATE_END || avail != W;
     uint32_t pos = 0, filled = 0;                             // stream indices: the ring holds [pos, filled)
     uint32_t stage[AR_BATCH];                                 // words [filled, filled + AR_FILL), on their way
@@ -280,6 +340,52 @@ __global__ void __launch_bounds__(AR_LANES) k_attr_rans_decode(const uint16_t* _
         atomicAdd(result, (unsigned long long)escapes);
         if (any_bad) atomicAdd(result + 1, 1ull);
     }
+}
+__global__ void __launch_bounds__(AR_LANES) k_attr_rans_decode(const uint16_t* __restrict__ table, const uint16_t* __restrict__ ctx, int64_t n, int S,
+                                                               const unsigned long long* __restrict__ states, const uint32_t* __restrict__ wcount,
+                                                               const uint32_t* __restrict__ offs, const uint32_t* __restrict__ words,
+                                                               int64_t words_total, int16_t* __restrict__ tokens,
+                                                               unsigned long long* __restrict__ result /*[0] tokens that are 63, [1] unsound chunks*/) {
+    __shared__ __attribute__((aligned(16))) uint32_t sh[AR_CONTEXTS * AR_ROW];
+    __shared__ uint32_t ring[AR_RING];
+    ar_load_table(sh, table);
+    const int64_t k = blockIdx.x, base = k * AR_LANES * S;
+    const int rows = (int)(n - base < (int64_t)AR_LANES * S ? n - base : (int64_t)AR_LANES * S);
+    ar_decode_chunk(sh, ring, ctx + base, rows, states + k * AR_LANES, wcount[k], (int64_t)offs[k], words, words_total, tokens + base, result);
+}
+
+// the contexts of a batch: position p of the batch's coding order lies in the last frame f with tok[f] <= 3 p, at position p - tok[f] / 3 of
+// that frame's own order, whose 65 offsets are row f of bucket [frames, 65]
+__global__ void __launch_bounds__(AR_SCAN_BLOCK) k_attr_rans_ctx_batch(const int32_t* __restrict__ bucket, ArFrames fr, uint16_t* __restrict__ ctx) {
+    const int64_t p = (int64_t)blockIdx.x * AR_SCAN_BLOCK + threadIdx.x;
+    if (3 * p >= fr.tok[fr.frames]) return;
+    int f = 0;
+    for (int b = 1; b < AR_MAX_FRAMES; ++b) f += (b < fr.frames && fr.tok[b] <= 3 * p) ? 1 : 0;
+    const int32_t* __restrict__ row = bucket + f * (AR_TOKENS + 1);
+    const int64_t q = p - fr.tok[f] / 3;
+    int b = 0;
+#pragma unroll
+    for (int step = 32; step > 0; step >>= 1) b += (b + step <= 63 && (int64_t)row[b + step] <= q) ? step : 0;         // b stays in 0 .. 63
+    const int d = 63 - b;
+    const uint16_t level = (uint16_t)(d / 3 < 15 ? d / 3 : 15);
+    ctx[3 * p] = level; ctx[3 * p + 1] = (uint16_t)(16 + level); ctx[3 * p + 2] = (uint16_t)(32 + level);          // (tok[] are multiples of 3)
+}
+// result [2 f], [2 f + 1]: frame f's tokens that are 63 and its unsound chunks
+__global__ void __launch_bounds__(AR_LANES) k_attr_rans_decode_batch(const uint16_t* __restrict__ tables, const uint16_t* __restrict__ ctx, ArFrames fr,
+                                                                     const uint8_t* __restrict__ payload, const uint32_t* __restrict__ offs,
+                                                                     int16_t* __restrict__ tokens, unsigned long long* __restrict__ result) {
+    __shared__ __attribute__((aligned(16))) uint32_t sh[AR_CONTEXTS * AR_ROW];
+    __shared__ uint32_t ring[AR_RING];
+    const int f = ar_frame_of(fr, blockIdx.x);
+    ar_load_table(sh, tables + (size_t)f * AR_CONTEXTS * (AR_TOKENS + 1));
+    const int S = fr.steps[f];
+    const int64_t k = (int64_t)blockIdx.x - fr.chunk[f], K = fr.chunk[f + 1] - fr.chunk[f], n = fr.tok[f + 1] - fr.tok[f];
+    const int64_t base = k * AR_LANES * S;
+    const int rows = (int)(n - base < (int64_t)AR_LANES * S ? n - base : (int64_t)AR_LANES * S);
+    const uint8_t* mine = payload + fr.pay[f];
+    const uint32_t* wcount = (const uint32_t*)(mine + 8 + 512 * K);
+    ar_decode_chunk(sh, ring, ctx + fr.tok[f] + base, rows, (const unsigned long long*)(mine + 8) + k * AR_LANES, wcount[k],
+                    (int64_t)offs[blockIdx.x], wcount + K, fr.words[f], tokens + fr.tok[f] + base, result + 2 * f);
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------------------
@@ -364,5 +470,113 @@ extern "C" int pcgc_attr_rans_decode(const uint16_t* table, const int32_t* bucke
     if (e != hipSuccess) { pcgc_set_error("attr_rans_decode: %s", hipGetErrorString(e)); return -1; }
     host2[0] = (int64_t)host[1];
     host2[1] = (int64_t)host[2] + (host[0] != words_total ? 1 : 0);      // unsound chunks (+ 1: the word counts do not add up to the payload)
+    return 0;
+}
+
+// ---- a batch of frames ------------------------------------------------------------------------------------------------------------------------
+// workspace: [slot: 64 x int64 = words per frame [16], then the encoder's refused tokens per frame [16] or the decoder's result [32]]
+//            [offs: K x u32, padded to 8 bytes][encoder: scratch, n x u32 | decoder: contexts, n x u16]
+extern "C" int64_t pcgc_attr_rans_batch_workspace_bytes(int64_t n, int64_t chunks) {
+    if (n < 0) n = 0;
+    if (chunks < 0) chunks = 0;
+    return 512 + (int64_t)ar_offs_bytes(chunks) + n * 4 + 64;
+}
+static long long* ar_host_slot_batch() {
+    static thread_local long long* host = nullptr;
+    if (!host && hipHostMalloc((void**)&host, 512, hipHostMallocDefault) != hipSuccess) host = nullptr;
+    return host;
+}
+// fills fr from the host arrays; false when they are not a batch: tok ascending multiples of 3 from 0, steps in range, K_f chunks each
+static bool ar_frames_of(int frames, const int64_t* tok, const int32_t* steps, const int64_t* pay, ArFrames& fr, bool all) {
+    memset(&fr, 0, sizeof(fr));
+    if (frames < 1 || frames > AR_MAX_FRAMES || !tok || !steps || !pay || tok[0] != 0) return false;
+    fr.frames = frames;
+    int64_t K = 0;
+    for (int f = 0; f < frames; ++f) {
+        const int64_t n = tok[f + 1] - tok[f];
+        if (n < 0 || n % 3 || tok[f + 1] >= ((int64_t)1 << 31) || steps[f] < 0 || steps[f] > AR_MAX_STEPS || (pay[f] & 7) || pay[f] < 0) return false;
+        if (all && n > 0 && steps[f] < 1) return false;
+        fr.tok[f] = tok[f]; fr.pay[f] = pay[f]; fr.steps[f] = steps[f]; fr.chunk[f] = (int)K;
+        K += (n > 0 && steps[f] > 0) ? ar_chunks(n, steps[f]) : 0;
+        if (K >= ((int64_t)1 << 31)) return false;
+    }
+    for (int f = frames; f <= AR_MAX_FRAMES; ++f) { fr.tok[f] = tok[frames]; fr.chunk[f] = (int)K; }
+    return true;
+}
+
+extern "C" int pcgc_attr_rans_encode_batch(const uint16_t* tables, const uint16_t* ctx, const int16_t* tokens, int frames, const int64_t* tok,
+                                           const int32_t* steps, uint8_t* payload, const int64_t* pay, int64_t* host, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    ArFrames fr;
+    PCGC_REQUIRE(ar_frames_of(frames, tok, steps, pay, fr, true), "1 to 16 frames; token offsets ascending multiples of 3 below 2^31; steps per chunk 1 .. 2^24; payload offsets multiples of 8");
+    PCGC_REQUIRE(tables && ctx && tokens && payload && host && ((uintptr_t)payload & 7) == 0, "null or misaligned argument");
+    const int64_t n = fr.tok[frames], K = fr.chunk[frames];
+    PCGC_REQUIRE(n >= 1, "no token: nothing to launch");
+    for (int f = 0; f < frames; ++f)
+        PCGC_REQUIRE(pay[f + 1] - pay[f] >= (fr.chunk[f + 1] > fr.chunk[f] ? 8 + 516 * (int64_t)(fr.chunk[f + 1] - fr.chunk[f]) + 4 * (tok[f + 1] - tok[f]) : 0),
+                     "payload room of a frame below 8 + 516 K + 4 n bytes");
+    PCGC_REQUIRE(workspace && workspace_bytes >= (size_t)pcgc_attr_rans_batch_workspace_bytes(n, K) && ((uintptr_t)workspace & 7) == 0, "workspace too small or misaligned");
+    long long* slot = (long long*)workspace;
+    uint32_t* offs = (uint32_t*)((char*)workspace + 512);
+    uint32_t* scratch = (uint32_t*)((char*)workspace + 512 + ar_offs_bytes(K));
+    long long* hostslot = ar_host_slot_batch();
+    if (!hostslot) { pcgc_set_error("attr_rans_encode_batch: cannot allocate pinned memory"); return -1; }
+    hipError_t e = hipMemsetAsync(slot, 0, 512, S(stream));
+    if (e != hipSuccess) { pcgc_set_error("attr_rans_encode_batch: %s", hipGetErrorString(e)); return -1; }
+    hipLaunchKernelGGL(k_attr_rans_encode_batch, dim3((unsigned)K), dim3(AR_LANES), 0, S(stream), tables, ctx, tokens, fr, scratch, payload,
+                       (unsigned long long*)(slot + AR_MAX_FRAMES));
+    PCGC_CHECK_LAUNCH("attr_rans_encode_batch");
+    hipLaunchKernelGGL(k_attr_rans_offsets_batch, dim3((unsigned)frames), dim3(AR_SCAN_BLOCK), 0, S(stream), fr, payload, offs, slot, 1);
+    PCGC_CHECK_LAUNCH("attr_rans_encode_batch");
+    hipLaunchKernelGGL(k_attr_rans_compact_batch, dim3((unsigned)K), dim3(AR_SCAN_BLOCK), 0, S(stream), (const uint32_t*)scratch, fr, (const uint32_t*)offs, payload);
+    PCGC_CHECK_LAUNCH("attr_rans_encode_batch");
+    e = hipMemcpyAsync(hostslot, slot, 2 * AR_MAX_FRAMES * sizeof(long long), hipMemcpyDeviceToHost, S(stream));
+    if (e == hipSuccess) e = hipStreamSynchronize(S(stream));
+    if (e != hipSuccess) { pcgc_set_error("attr_rans_encode_batch: %s", hipGetErrorString(e)); return -1; }
+    for (int f = 0; f < frames; ++f) {
+        const int64_t Kf = fr.chunk[f + 1] - fr.chunk[f];
+        host[f] = Kf ? 8 + 516 * Kf + 4 * (int64_t)hostslot[f] : 0;
+        host[frames + f] = (int64_t)hostslot[AR_MAX_FRAMES + f];
+    }
+    return 0;
+}
+
+extern "C" int pcgc_attr_rans_decode_batch(const uint16_t* tables, const int32_t* bucket, int frames, const int64_t* tok, const int32_t* steps,
+                                           const uint8_t* payload, const int64_t* pay, const int64_t* pay_bytes, int16_t* tokens, int64_t* host,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+    ArFrames fr;
+    PCGC_REQUIRE(ar_frames_of(frames, tok, steps, pay, fr, false), "1 to 16 frames; token offsets ascending multiples of 3 below 2^31; steps per chunk 0 .. 2^24; payload offsets multiples of 8");
+    PCGC_REQUIRE(tables && bucket && tokens && payload && pay_bytes && host && ((uintptr_t)payload & 7) == 0, "null or misaligned argument");
+    const int64_t n = fr.tok[frames], K = fr.chunk[frames];
+    PCGC_REQUIRE(n >= 1 && K >= 1, "no chunk: nothing to launch");
+    for (int f = 0; f < frames; ++f) {
+        const int64_t Kf = fr.chunk[f + 1] - fr.chunk[f];
+        if (!Kf) continue;
+        PCGC_REQUIRE(pay_bytes[f] >= 8 + 516 * Kf && (pay_bytes[f] - 8 - 516 * Kf) % 4 == 0, "a payload cut inside its tables or not whole words");
+        fr.words[f] = (pay_bytes[f] - 8 - 516 * Kf) / 4;
+    }
+    PCGC_REQUIRE(workspace && workspace_bytes >= (size_t)pcgc_attr_rans_batch_workspace_bytes(n, K) && ((uintptr_t)workspace & 7) == 0, "workspace too small or misaligned");
+    long long* slot = (long long*)workspace;
+    uint32_t* offs = (uint32_t*)((char*)workspace + 512);
+    uint16_t* ctx = (uint16_t*)((char*)workspace + 512 + ar_offs_bytes(K));
+    long long* hostslot = ar_host_slot_batch();
+    if (!hostslot) { pcgc_set_error("attr_rans_decode_batch: cannot allocate pinned memory"); return -1; }
+    hipError_t e = hipMemsetAsync(slot, 0, 512, S(stream));
+    if (e != hipSuccess) { pcgc_set_error("attr_rans_decode_batch: %s", hipGetErrorString(e)); return -1; }
+    hipLaunchKernelGGL(k_attr_rans_ctx_batch, dim3(grid_for(n / 3, AR_SCAN_BLOCK)), dim3(AR_SCAN_BLOCK), 0, S(stream), bucket, fr, ctx);
+    PCGC_CHECK_LAUNCH("attr_rans_decode_batch");
+    hipLaunchKernelGGL(k_attr_rans_offsets_batch, dim3((unsigned)frames), dim3(AR_SCAN_BLOCK), 0, S(stream), fr, const_cast<uint8_t*>(payload), offs, slot, 0);
+    PCGC_CHECK_LAUNCH("attr_rans_decode_batch");
+    hipLaunchKernelGGL(k_attr_rans_decode_batch, dim3((unsigned)K), dim3(AR_LANES), 0, S(stream), tables, (const uint16_t*)ctx, fr, payload,
+                       (const uint32_t*)offs, tokens, (unsigned long long*)(slot + AR_MAX_FRAMES));
+    PCGC_CHECK_LAUNCH("attr_rans_decode_batch");
+    e = hipMemcpyAsync(hostslot, slot, 3 * AR_MAX_FRAMES * sizeof(long long), hipMemcpyDeviceToHost, S(stream));
+    if (e == hipSuccess) e = hipStreamSynchronize(S(stream));
+    if (e != hipSuccess) { pcgc_set_error("attr_rans_decode_batch: %s", hipGetErrorString(e)); return -1; }
+    for (int f = 0; f < frames; ++f) {
+        const bool here = fr.chunk[f + 1] > fr.chunk[f];
+        host[f] = here ? (int64_t)hostslot[AR_MAX_FRAMES + 2 * f] : 0;
+        host[frames + f] = here ? (int64_t)hostslot[AR_MAX_FRAMES + 2 * f + 1] + (hostslot[f] != fr.words[f] ? 1 : 0) : 0;
+    }
     return 0;
 }

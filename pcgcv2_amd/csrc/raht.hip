@@ -20,6 +20,12 @@
 //                         The three channels travel as one int32 x 3.
 //   pcgc_raht_quantize    levels, tokens, contexts, escape remainders (compacted behind pcgc_mask_scan) and the [48, 64] histogram
 //   pcgc_raht_dequantize  tokens and escapes -> H^ per gap
+//
+// A BATCH of up to RAHT_MAX_FRAMES frames goes through the same steps once (pcgc_raht_*_batch): the frame index is bits
+// 60 .. 63 of the key, so after ONE sort frame b is a run of leaves and every gap with d < 60 lies inside one frame, with the lo / hi /
+// children it has in that frame alone (shifted by the run's start): the searches above compare whole keys.  The B - 1 gaps with d >= 60
+// are frame boundaries: no merge, no token; they get lo = hi = -1, which every transform kernel already leaves alone.  The coding order
+// is frame, then d descending, then gap ascending, the boundaries behind it; each frame's DC is the value at the start of its run.
 #include <cstring>
 #include "pcgc_common.h"
 #include <rocprim/rocprim.hpp>
@@ -31,6 +37,8 @@
 #define RAHT_SPINE_THREADS 1024
 #define RAHT_CONTEXTS 48
 #define RAHT_ESCAPE 63
+#define RAHT_MAX_FRAMES 16                   // the batch index is a 4-bit field everywhere (pcgc_common.h); here key bits 60 .. 63
+#define RAHT_FRAME_BIT 60
 
 struct i3 { int32_t a, b, c; };              // (Y, Co, Cg), or the three H of a gap
 
@@ -96,8 +104,84 @@ extern "C" int pcgc_raht_keys(const int32_t* coords, int64_t n, uint64_t* keys, 
     return 0;
 }
 
+// status [34]: [0 .. 15] adjacent equal keys per frame, [16 .. 31] rows per frame, [32] bit 0 = a coordinate outside [0, 2^20), bit 1 = a frame
+// index outside 0 .. B - 1
+__global__ void __launch_bounds__(256) k_raht_keys_batch(const int4* __restrict__ coords, int64_t n, int B, uint64_t* __restrict__ keys,
+                                                         int32_t* __restrict__ idx, int32_t* status) {
+    __shared__ int32_t cnt[RAHT_MAX_FRAMES];
+    if (threadIdx.x < RAHT_MAX_FRAMES) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const int4 c = coords[i];
+        const int bad = ((((uint32_t)c.y | (uint32_t)c.z | (uint32_t)c.w) >> 20) ? 1 : 0) | ((uint32_t)c.x >= (uint32_t)B ? 2 : 0);
+        if (bad) atomicOr(status + 32, bad);
+        const uint32_t f = (uint32_t)c.x & (RAHT_MAX_FRAMES - 1);
+        const uint64_t m = spread3((uint32_t)c.y) | (spread3((uint32_t)c.z) << 1) | (spread3((uint32_t)c.w) << 2);
+        keys[i] = (m & ((1ull << RAHT_FRAME_BIT) - 1)) | ((uint64_t)f << RAHT_FRAME_BIT);
+        idx[i] = (int32_t)i;
+        if (!(bad & 2)) atomicAdd(&cnt[f], 1);
+    }
+    __syncthreads();
+    if (threadIdx.x < RAHT_MAX_FRAMES && cnt[threadIdx.x]) atomicAdd(status + 16 + threadIdx.x, cnt[threadIdx.x]);
+}
+__global__ void __launch_bounds__(256) k_raht_dups_batch(const uint64_t* __restrict__ keys, int64_t n, int32_t* status) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i + 1 < n && keys[i] == keys[i + 1]) atomicAdd(status + (int)(keys[i] >> RAHT_FRAME_BIT), 1);
+}
+extern "C" int64_t pcgc_raht_keys_batch_workspace_bytes(int64_t n) {
+    if (n < 1) n = 1;
+    return (int64_t)(align256((size_t)n * 8) + align256((size_t)n * 4) + align256(sort_temp_bytes<uint64_t>(n, 64)));
+}
+extern "C" int pcgc_raht_keys_batch(const int32_t* coords, int64_t n, int frames, uint64_t* keys, int32_t* perm, int32_t* status, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
+    PCGC_REQUIRE(frames >= 1 && frames <= RAHT_MAX_FRAMES, "1 to 16 frames");
+    PCGC_REQUIRE(coords && keys && perm && status && workspace, "null argument");
+    PCGC_REQUIRE(workspace_bytes >= (size_t)pcgc_raht_keys_batch_workspace_bytes(n), "workspace too small");
+    char* ws = (char*)workspace;
+    uint64_t* kin = (uint64_t*)ws; ws += align256((size_t)n * 8);
+    int32_t* idx = (int32_t*)ws; ws += align256((size_t)n * 4);
+    size_t tmp = sort_temp_bytes<uint64_t>(n, 64);
+    hipError_t e = hipMemsetAsync(status, 0, 34 * sizeof(int32_t), S(stream));
+    if (e != hipSuccess) { pcgc_set_error("raht_keys_batch: %s", hipGetErrorString(e)); return -1; }
+    hipLaunchKernelGGL(k_raht_keys_batch, dim3(grid_for(n, 256)), dim3(256), 0, S(stream), (const int4*)coords, n, frames, kin, idx, status);
+    PCGC_CHECK_LAUNCH("raht_keys_batch");
+    e = rocprim::radix_sort_pairs((void*)ws, tmp, kin, keys, idx, perm, (size_t)n, 0, 64, S(stream));      // (unsigned: frames 8 .. 15 set bit 63)
+    if (e != hipSuccess) { pcgc_set_error("raht_keys_batch: %s", hipGetErrorString(e)); return -1; }
+    hipLaunchKernelGGL(k_raht_dups_batch, dim3(grid_for(n, 256)), dim3(256), 0, S(stream), keys, n, status);
+    PCGC_CHECK_LAUNCH("raht_keys_batch");
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------------------------ tree
 __device__ static inline int msb64(uint64_t v) { return 63 - __clzll((long long)v); }
+
+// gap g of split bit d = msb(key_g ^ key_{g+1}): the range [lo, hi] of the merged node and its two children (a gap, or ~leaf)
+__device__ static inline void tree_gap(const uint64_t* __restrict__ keys, int64_t n, int64_t g, int d, int64_t& lo, int64_t& hi, int32_t& left,
+                                   int32_t& right) {
+    const uint64_t ki = keys[g], kj = keys[g + 1];
+    int64_t a = 0, b = g;                                  // lo: the first leaf that shares key_i's bits above d
+    while (a < b) { const int64_t m = (a + b) >> 1; if (((keys[m] ^ ki) >> (d + 1)) == 0) b = m; else a = m + 1; }
+    lo = a;
+    a = g + 1; b = n - 1;                                  // hi: the last one
+    while (a < b) { const int64_t m = (a + b + 1) >> 1; if (((keys[m] ^ kj) >> (d + 1)) == 0) a = m; else b = m - 1; }
+    hi = a;
+    left = ~(int32_t)g; right = ~(int32_t)(g + 1);
+    if (lo < g) {                                          // the split of [lo, g]: the last leaf whose bit dl is key_lo's
+        const uint64_t kl = keys[lo];
+        const int dl = msb64((kl ^ ki) | 1ull);
+        a = lo; b = g - 1;
+        while (a < b) { const int64_t m = (a + b + 1) >> 1; if (((keys[m] ^ kl) >> dl) == 0) a = m; else b = m - 1; }
+        left = (int32_t)a;
+    }
+    if (hi > g + 1) {
+        const int dr = msb64((kj ^ keys[hi]) | 1ull);
+        a = g + 1; b = hi - 1;
+        while (a < b) { const int64_t m = (a + b + 1) >> 1; if (((keys[m] ^ kj) >> dr) == 0) a = m; else b = m - 1; }
+        right = (int32_t)a;
+    }
+}
 
 // cnt [128]: gaps per split bit, all (0 .. 63) and those whose range crosses a tile boundary (64 .. 127)
 __global__ void __launch_bounds__(256) k_raht_tree(const uint64_t* __restrict__ keys, int64_t n, int32_t tile, uint8_t* __restrict__ d8,
@@ -109,28 +193,10 @@ __global__ void __launch_bounds__(256) k_raht_tree(const uint64_t* __restrict__ 
     __syncthreads();
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g < n - 1) {
-        const uint64_t ki = keys[g], kj = keys[g + 1];
-        const int d = msb64((ki ^ kj) | 1ull);                 // (| 1: equal keys are refused by the caller; this keeps the shifts defined)
-        int64_t a = 0, b = g;                                  // lo: the first leaf that shares key_i's bits above d
-        while (a < b) { const int64_t m = (a + b) >> 1; if (((keys[m] ^ ki) >> (d + 1)) == 0) b = m; else a = m + 1; }
-        const int64_t lo = a;
-        a = g + 1; b = n - 1;                                  // hi: the last one
-        while (a < b) { const int64_t m = (a + b + 1) >> 1; if (((keys[m] ^ kj) >> (d + 1)) == 0) a = m; else b = m - 1; }
-        const int64_t hi = a;
-        int32_t left = ~(int32_t)g, right = ~(int32_t)(g + 1);
-        if (lo < g) {                                          // the split of [lo, g]: the last leaf whose bit dl is key_lo's
-            const uint64_t kl = keys[lo];
-            const int dl = msb64((kl ^ ki) | 1ull);
-            a = lo; b = g - 1;
-            while (a < b) { const int64_t m = (a + b + 1) >> 1; if (((keys[m] ^ kl) >> dl) == 0) a = m; else b = m - 1; }
-            left = (int32_t)a;
-        }
-        if (hi > g + 1) {
-            const int dr = msb64((kj ^ keys[hi]) | 1ull);
-            a = g + 1; b = hi - 1;
-            while (a < b) { const int64_t m = (a + b + 1) >> 1; if (((keys[m] ^ kj) >> dr) == 0) a = m; else b = m - 1; }
-            right = (int32_t)a;
-        }
+        const int d = msb64((keys[g] ^ keys[g + 1]) | 1ull);   // (| 1: equal keys are refused by the caller; this keeps the shifts defined)
+        int64_t lo, hi;
+        int32_t left, right;
+        tree_gap(keys, n, g, d, lo, hi, left, right);
         const int cross = (lo / tile) != (hi / tile);
         d8[g] = (uint8_t)d; lo_o[g] = (int32_t)lo; hi_o[g] = (int32_t)hi; left_o[g] = left; right_o[g] = right;
         skey[g] = (uint8_t)(63 - d); skey_cross[g] = (uint8_t)((63 - d) | (cross ? 0 : 64));
@@ -182,6 +248,90 @@ extern "C" int pcgc_raht_tree(const uint64_t* keys, int64_t n, uint8_t* d, int32
     }
     hipLaunchKernelGGL(k_raht_offsets, dim3(1), dim3(64), 0, S(stream), cnt, offsets);
     PCGC_CHECK_LAUNCH("raht_tree");
+    return 0;
+}
+
+// The tree of a batch.  cnt [17 x 64]: gaps per frame and split bit, then (row 16) those of all frames whose range crosses a tile boundary.
+// A frame boundary (d >= 60) is no merge: lo = hi = -1, no children, counted nowhere, sorted behind everything.
+#define RAHT_BATCH_CNT ((RAHT_MAX_FRAMES + 1) * 64)
+__global__ void __launch_bounds__(256) k_raht_tree_batch(const uint64_t* __restrict__ keys, int64_t n, int32_t tile, uint8_t* __restrict__ d8,
+                                                         int32_t* __restrict__ lo_o, int32_t* __restrict__ hi_o, int32_t* __restrict__ left_o,
+                                                         int32_t* __restrict__ right_o, uint16_t* __restrict__ skey,
+                                                         uint8_t* __restrict__ skey_cross, int32_t* __restrict__ idx, int32_t* cnt) {
+    __shared__ int32_t h[RAHT_BATCH_CNT];
+    for (int j = threadIdx.x; j < RAHT_BATCH_CNT; j += 256) h[j] = 0;
+    __syncthreads();
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < n - 1) {
+        const int d = msb64((keys[g] ^ keys[g + 1]) | 1ull);
+        idx[g] = (int32_t)g;
+        d8[g] = (uint8_t)d;
+        if (d >= RAHT_FRAME_BIT) {
+            lo_o[g] = -1; hi_o[g] = -1; left_o[g] = ~(int32_t)g; right_o[g] = ~(int32_t)(g + 1);
+            skey[g] = (uint16_t)(RAHT_MAX_FRAMES * 64); skey_cross[g] = 128;
+        } else {
+            int64_t lo, hi;
+            int32_t left, right;
+            tree_gap(keys, n, g, d, lo, hi, left, right);
+            const int cross = (lo / tile) != (hi / tile);
+            const int f = (int)(keys[g] >> RAHT_FRAME_BIT);
+            lo_o[g] = (int32_t)lo; hi_o[g] = (int32_t)hi; left_o[g] = left; right_o[g] = right;
+            skey[g] = (uint16_t)(f * 64 + 63 - d); skey_cross[g] = (uint8_t)((63 - d) | (cross ? 0 : 64));
+            atomicAdd(&h[f * 64 + d], 1);
+            if (cross) atomicAdd(&h[RAHT_MAX_FRAMES * 64 + d], 1);
+        }
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < RAHT_BATCH_CNT; j += 256) if (h[j]) atomicAdd(cnt + j, h[j]);
+}
+// offsets [(frames + 1) x 65]: bucket [65] of every frame (counted from the frame's own first gap), then cross [65] of the batch
+__global__ void k_raht_offsets_batch(const int32_t* __restrict__ cnt, int frames, int32_t* __restrict__ offsets) {
+    if ((int)threadIdx.x <= frames) {
+        const int32_t* c = cnt + 64 * ((int)threadIdx.x < frames ? threadIdx.x : RAHT_MAX_FRAMES);
+        int32_t* o = offsets + 65 * threadIdx.x;
+        int32_t acc = 0;
+        for (int b = 0; b < 64; ++b) { o[b] = acc; acc += c[63 - b]; }
+        o[64] = acc;
+    }
+}
+
+extern "C" int64_t pcgc_raht_tree_batch_workspace_bytes(int64_t n) {
+    const size_t g = (size_t)(n < 2 ? 1 : n - 1);
+    return (int64_t)(2 * align256(g * 2) + 2 * align256(g) + align256(g * 4) + align256(RAHT_BATCH_CNT * 4) +
+                     align256(sort_temp_bytes<uint16_t>((int64_t)g, 11)) + align256(sort_temp_bytes<uint8_t>((int64_t)g, 8)));
+}
+extern "C" int pcgc_raht_tree_batch(const uint64_t* keys, int64_t n, int frames, uint8_t* d, int32_t* lo, int32_t* hi, int32_t* left, int32_t* right,
+                                    int32_t* order, int32_t* cross_order, int32_t* offsets, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+    PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
+    PCGC_REQUIRE(frames >= 1 && frames <= RAHT_MAX_FRAMES, "1 to 16 frames");
+    PCGC_REQUIRE(offsets && workspace, "null argument");
+    PCGC_REQUIRE(workspace_bytes >= (size_t)pcgc_raht_tree_batch_workspace_bytes(n), "workspace too small");
+    const int64_t g = n - 1;
+    const size_t g1 = (size_t)(g < 1 ? 1 : g);
+    char* ws = (char*)workspace;
+    uint16_t* skey = (uint16_t*)ws; ws += align256(g1 * 2);
+    uint16_t* sorted = (uint16_t*)ws; ws += align256(g1 * 2);
+    uint8_t* skey_cross = (uint8_t*)ws; ws += align256(g1);
+    uint8_t* sorted_cross = (uint8_t*)ws; ws += align256(g1);
+    int32_t* idx = (int32_t*)ws; ws += align256(g1 * 4);
+    int32_t* cnt = (int32_t*)ws; ws += align256(RAHT_BATCH_CNT * 4);
+    hipError_t e = hipMemsetAsync(cnt, 0, RAHT_BATCH_CNT * 4, S(stream));
+    if (e != hipSuccess) { pcgc_set_error("raht_tree_batch: %s", hipGetErrorString(e)); return -1; }
+    if (g > 0) {
+        PCGC_REQUIRE(keys && d && lo && hi && left && right && order && cross_order, "null argument");
+        hipLaunchKernelGGL(k_raht_tree_batch, dim3(grid_for(g, 256)), dim3(256), 0, S(stream), keys, n, (int32_t)RAHT_TILE, d, lo, hi, left, right,
+                           skey, skey_cross, idx, cnt);
+        PCGC_CHECK_LAUNCH("raht_tree_batch");
+        size_t tmp = sort_temp_bytes<uint16_t>(g, 11);
+        e = rocprim::radix_sort_pairs((void*)ws, tmp, skey, sorted, idx, order, (size_t)g, 0, 11, S(stream));
+        ws += align256(tmp);
+        tmp = sort_temp_bytes<uint8_t>(g, 8);
+        if (e == hipSuccess) e = rocprim::radix_sort_pairs((void*)ws, tmp, skey_cross, sorted_cross, idx, cross_order, (size_t)g, 0, 8, S(stream));
+        if (e != hipSuccess) { pcgc_set_error("raht_tree_batch: %s", hipGetErrorString(e)); return -1; }
+    }
+    hipLaunchKernelGGL(k_raht_offsets_batch, dim3(1), dim3(64), 0, S(stream), cnt, frames, offsets);
+    PCGC_CHECK_LAUNCH("raht_tree_batch");
     return 0;
 }
 
@@ -422,6 +572,70 @@ extern "C" int pcgc_raht_inverse(const int32_t* Hhat, int32_t dc_y, int32_t dc_c
     return 0;
 }
 
+// A batch.  The kernels are the ones above: a frame boundary has lo = hi = -1, so the tile kernel does not take it (l >= s fails), it is in
+// no list the other two walk, and ranges of one split bit are disjoint across frames as they are inside one.  Form 0 walks cross_order,
+// which lists every split bit twice (the crossing gaps, then the others): bit_off [130] on the HOST holds both sets of 65 offsets.
+__global__ void k_raht_set_dc_batch(i3* val, int64_t n, const int32_t* __restrict__ starts, const i3* __restrict__ dc, int frames) {
+    const int b = threadIdx.x;
+    if (b < frames && starts[b] >= 0 && starts[b] < n) val[starts[b]] = dc[b];
+}
+static bool bit_offsets_sound(const int32_t* off, int64_t n) {
+    if (off[0] != 0 || off[65] != off[64]) return false;
+    for (int b = 0; b < 64; ++b) if (off[b + 1] < off[b] || off[65 + b + 1] < off[65 + b]) return false;
+    return off[129] <= n - 1;
+}
+template <bool FWD>
+static int raht_run_batch(const uint8_t* rgb_in, uint8_t* rgb_out, const int32_t* perm, int64_t n, const uint8_t* d, const int32_t* lo,
+                          const int32_t* hi, const int32_t* cross_order, const int32_t* bit_off, const int32_t* cross_off_dev, int form,
+                          const int32_t* starts, const i3* dc, int frames, i3* val, i3* H, hipStream_t s) {
+    const unsigned tiles = grid_for(n, RAHT_TILE);
+    if (!FWD) hipLaunchKernelGGL(k_raht_set_dc_batch, dim3(1), dim3(64), 0, s, val, n, starts, dc, frames);
+    if (form == 0) {
+        if (FWD) hipLaunchKernelGGL(k_raht_load, dim3(grid_for(n, 256)), dim3(256), 0, s, rgb_in, perm, n, val);
+        for (int k = 0; k < 64; ++k) {
+            const int b = FWD ? 63 - k : k;
+            for (int half = 0; half < 2; ++half) {
+                const int64_t begin = bit_off[65 * half + b], end = bit_off[65 * half + b + 1];
+                if (begin < end)
+                    hipLaunchKernelGGL(k_raht_bit<FWD>, dim3(grid_for(end - begin, 256)), dim3(256), 0, s, cross_order, begin, end, n, lo, hi, val, H);
+            }
+        }
+        if (!FWD) hipLaunchKernelGGL(k_raht_store, dim3(grid_for(n, 256)), dim3(256), 0, s, val, perm, n, rgb_out);
+    } else {
+        if (FWD) hipLaunchKernelGGL(k_raht_tile<true>, dim3(tiles), dim3(RAHT_THREADS), 0, s, rgb_in, rgb_out, perm, n, d, lo, hi, val, H);
+        if (tiles > 1)
+            hipLaunchKernelGGL(k_raht_spine<FWD>, dim3(1), dim3(RAHT_SPINE_THREADS), 0, s, cross_order, cross_off_dev, n, lo, hi, val, H);
+        if (!FWD) hipLaunchKernelGGL(k_raht_tile<false>, dim3(tiles), dim3(RAHT_THREADS), 0, s, rgb_in, rgb_out, perm, n, d, lo, hi, val, H);
+    }
+    return 0;
+}
+extern "C" int pcgc_raht_forward_batch(const uint8_t* rgb, const int32_t* perm, int64_t n, const uint8_t* d, const int32_t* lo, const int32_t* hi,
+                                       const int32_t* cross_order, const int32_t* bit_off, const int32_t* cross_off, int form, int32_t* val,
+                                       int32_t* H, void* stream) {
+    PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
+    PCGC_REQUIRE(form == 0 || form == 1, "form 0 (one launch per split bit) or 1 (tiles)");
+    PCGC_REQUIRE(rgb && perm && val && bit_off && cross_off, "null argument");
+    PCGC_REQUIRE(n == 1 || (d && lo && hi && cross_order && H), "null argument");
+    PCGC_REQUIRE(bit_offsets_sound(bit_off, n), "bit offsets are not those of a batch tree of n leaves");
+    raht_run_batch<true>(rgb, nullptr, perm, n, d, lo, hi, cross_order, bit_off, cross_off, form, nullptr, nullptr, 0, (i3*)val, (i3*)H, S(stream));
+    PCGC_CHECK_LAUNCH("raht_forward_batch");
+    return 0;
+}
+extern "C" int pcgc_raht_inverse_batch(const int32_t* Hhat, const int32_t* dc, const int32_t* starts, int frames, const int32_t* perm, int64_t n,
+                                       const uint8_t* d, const int32_t* lo, const int32_t* hi, const int32_t* cross_order, const int32_t* bit_off,
+                                       const int32_t* cross_off, int form, int32_t* val, uint8_t* rgb, void* stream) {
+    PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
+    PCGC_REQUIRE(frames >= 1 && frames <= RAHT_MAX_FRAMES, "1 to 16 frames");
+    PCGC_REQUIRE(form == 0 || form == 1, "form 0 (one launch per split bit) or 1 (tiles)");
+    PCGC_REQUIRE(rgb && perm && val && bit_off && cross_off && dc && starts, "null argument");
+    PCGC_REQUIRE(n == 1 || (d && lo && hi && cross_order && Hhat), "null argument");
+    PCGC_REQUIRE(bit_offsets_sound(bit_off, n), "bit offsets are not those of a batch tree of n leaves");
+    raht_run_batch<false>(nullptr, rgb, perm, n, d, lo, hi, cross_order, bit_off, cross_off, form, starts, (const i3*)dc, frames, (i3*)val,
+                          (i3*)const_cast<int32_t*>(Hhat), S(stream));
+    PCGC_CHECK_LAUNCH("raht_inverse_batch");
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------------------------ quantiser
 __device__ static inline uint32_t isqrt64(uint64_t v) {       // v < 2^52
     uint64_t r = 0;
@@ -565,5 +779,167 @@ extern "C" int pcgc_raht_dequantize(const int16_t* tokens, const uint16_t* escap
     hipLaunchKernelGGL(k_raht_dequantize, dim3(grid_for(gaps, 256)), dim3(256), 0, S(stream), tokens, prefix, escapes, n_escapes, gaps, lo, hi, order,
                        q_luma, q_chroma, (i3*)Hhat);
     PCGC_CHECK_LAUNCH("raht_dequantize");
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ quantiser, a batch
+// coded = n - frames positions of the batch's coding order (the frame boundaries lie behind them); the frame of a position is bits 60 .. 63
+// of its gap's key, its steps come from a table passed by value
+struct RahtSteps { uint8_t luma[RAHT_MAX_FRAMES], chroma[RAHT_MAX_FRAMES]; };
+
+__global__ void __launch_bounds__(256) k_raht_quantize_batch(const i3* __restrict__ H, int64_t coded, int64_t gaps, const uint64_t* __restrict__ keys,
+                                                             const uint8_t* __restrict__ d8, const int32_t* __restrict__ lo,
+                                                             const int32_t* __restrict__ hi, const int32_t* __restrict__ order, RahtSteps q,
+                                                             int16_t* __restrict__ tokens, uint16_t* __restrict__ ctx, uint8_t* __restrict__ escmask,
+                                                             uint16_t* __restrict__ rem, int32_t* hist) {
+    // the block's LDS histogram is that of the frame of its first position; the few positions of a block that belong to a later frame go
+    // to the global histogram directly (integer atomics either way: the sums do not depend on the order)
+    __shared__ int32_t h[RAHT_CONTEXTS * 64];
+    __shared__ int f0_s;
+    for (int j = threadIdx.x; j < RAHT_CONTEXTS * 64; j += 256) h[j] = 0;
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int32_t g = -1;
+    int f = -1;
+    if (p < coded) {
+        g = order[p];
+        if (g >= 0 && g < gaps && d8[g] < RAHT_FRAME_BIT && lo[g] >= 0) f = (int)(keys[g] >> RAHT_FRAME_BIT); else g = -1;
+    }
+    if (threadIdx.x == 0) f0_s = f;
+    __syncthreads();
+    const int f0 = f0_s;
+    if (g >= 0) {
+        const int64_t w1 = g - lo[g] + 1, w2 = hi[g] - g;
+        const i3 v = H[g];
+        const int64_t dl = delta16(q.luma[f], w1, w2), dc = delta16(q.chroma[f], w1, w2);
+        const int row = d8[g] / 3 < 15 ? d8[g] / 3 : 15;
+        const int32_t z[3] = {level_z(v.a, dl), level_z(v.b, dc), level_z(v.c, dc)};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int t = z[c] < RAHT_ESCAPE ? z[c] : RAHT_ESCAPE;
+            tokens[3 * p + c] = (int16_t)t;
+            ctx[3 * p + c] = (uint16_t)(16 * c + row);
+            escmask[3 * p + c] = t == RAHT_ESCAPE;
+            rem[3 * p + c] = (uint16_t)(t == RAHT_ESCAPE ? z[c] - RAHT_ESCAPE : 0);
+            if (f == f0) atomicAdd(&h[(16 * c + row) * 64 + t], 1);
+            else atomicAdd(hist + ((int64_t)f * RAHT_CONTEXTS + 16 * c + row) * 64 + t, 1);
+        }
+    } else if (p < coded) {                                    // (never, for a tree pcgc_raht_tree_batch built)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { tokens[3 * p + c] = 0; ctx[3 * p + c] = (uint16_t)(16 * c); escmask[3 * p + c] = 0; rem[3 * p + c] = 0; }
+    }
+    __syncthreads();
+    if (f0 >= 0)
+        for (int j = threadIdx.x; j < RAHT_CONTEXTS * 64; j += 256) if (h[j]) atomicAdd(hist + (int64_t)f0 * RAHT_CONTEXTS * 64 + j, h[j]);
+}
+
+static bool steps_of(const int32_t* q_luma, const int32_t* q_chroma, int frames, RahtSteps& q) {
+    memset(&q, 0, sizeof(q));
+    for (int b = 0; b < frames; ++b) {
+        if (q_luma[b] < 0 || q_luma[b] > 255 || q_chroma[b] < 0 || q_chroma[b] > 255) return false;
+        q.luma[b] = (uint8_t)q_luma[b]; q.chroma[b] = (uint8_t)q_chroma[b];
+    }
+    return true;
+}
+static size_t tokens_of_batch(int64_t n, int frames) { return (size_t)(n - frames < 1 ? 1 : 3 * (n - frames)); }
+
+extern "C" int64_t pcgc_raht_quantize_batch_workspace_bytes(int64_t n, int frames) {
+    const size_t t = tokens_of_batch(n, frames);
+    return (int64_t)(align256(t) + align256(t * 2) + align256(t * 4) + align256(pcgc_scan_workspace_bytes((int64_t)t)));
+}
+extern "C" int pcgc_raht_quantize_batch(const int32_t* H, int64_t n, int frames, const uint64_t* keys, const uint8_t* d, const int32_t* lo,
+                                        const int32_t* hi, const int32_t* order, const int32_t* q_luma, const int32_t* q_chroma, int16_t* tokens,
+                                        uint16_t* ctx, uint16_t* escapes, int32_t* n_escapes, int32_t* hist, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+    PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
+    PCGC_REQUIRE(frames >= 1 && frames <= RAHT_MAX_FRAMES && frames <= n, "1 to 16 frames of at least one point");
+    PCGC_REQUIRE(q_luma && q_chroma && n_escapes && hist && workspace, "null argument");
+    RahtSteps q;
+    PCGC_REQUIRE(steps_of(q_luma, q_chroma, frames, q), "quantiser 0 .. 255");
+    PCGC_REQUIRE(workspace_bytes >= (size_t)pcgc_raht_quantize_batch_workspace_bytes(n, frames), "workspace too small");
+    hipError_t e = hipMemsetAsync(hist, 0, (size_t)frames * RAHT_CONTEXTS * 64 * sizeof(int32_t), S(stream));
+    if (e == hipSuccess) e = hipMemsetAsync(n_escapes, 0, sizeof(int32_t), S(stream));
+    if (e != hipSuccess) { pcgc_set_error("raht_quantize_batch: %s", hipGetErrorString(e)); return -1; }
+    if (n == frames) return 0;
+    PCGC_REQUIRE(H && keys && d && lo && hi && order && tokens && ctx && escapes, "null argument");
+    const int64_t coded = n - frames, t = 3 * coded;
+    char* ws = (char*)workspace;
+    uint8_t* escmask = (uint8_t*)ws; ws += align256((size_t)t);
+    uint16_t* rem = (uint16_t*)ws; ws += align256((size_t)t * 2);
+    int32_t* prefix = (int32_t*)ws; ws += align256((size_t)t * 4);
+    hipLaunchKernelGGL(k_raht_quantize_batch, dim3(grid_for(coded, 256)), dim3(256), 0, S(stream), (const i3*)H, coded, n - 1, keys, d, lo, hi, order,
+                       q, tokens, ctx, escmask, rem, hist);
+    PCGC_CHECK_LAUNCH("raht_quantize_batch");
+    if (pcgc_mask_scan(escmask, t, prefix, n_escapes, ws, pcgc_scan_workspace_bytes(t), stream) != 0) return -1;
+    hipLaunchKernelGGL(k_raht_compact_esc, dim3(grid_for(t, 256)), dim3(256), 0, S(stream), escmask, prefix, rem, t, escapes);
+    PCGC_CHECK_LAUNCH("raht_quantize_batch");
+    return 0;
+}
+
+// the mask of the tokens that are 63, and how many of them each frame has (counts [16], zeroed by the caller)
+__global__ void __launch_bounds__(256) k_raht_escmask_batch(const int16_t* __restrict__ tokens, int64_t n, const int32_t* __restrict__ order,
+                                                            const uint64_t* __restrict__ keys, int64_t gaps, uint8_t* __restrict__ escmask,
+                                                            int32_t* counts) {
+    __shared__ int32_t c[RAHT_MAX_FRAMES];
+    if (threadIdx.x < RAHT_MAX_FRAMES) c[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const bool m = tokens[i] == RAHT_ESCAPE;
+        escmask[i] = m;
+        if (m) { const int32_t g = order[i / 3]; if (g >= 0 && g < gaps) atomicAdd(&c[(int)(keys[g] >> RAHT_FRAME_BIT)], 1); }
+    }
+    __syncthreads();
+    if (threadIdx.x < RAHT_MAX_FRAMES && c[threadIdx.x]) atomicAdd(counts + threadIdx.x, c[threadIdx.x]);
+}
+__global__ void __launch_bounds__(256) k_raht_dequantize_batch(const int16_t* __restrict__ tokens, const int32_t* __restrict__ prefix,
+                                                               const uint16_t* __restrict__ esc, int64_t n_esc, int64_t coded, int64_t gaps,
+                                                               const uint64_t* __restrict__ keys, const int32_t* __restrict__ lo,
+                                                               const int32_t* __restrict__ hi, const int32_t* __restrict__ order, RahtSteps q,
+                                                               i3* __restrict__ Hhat) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= coded) return;
+    const int32_t g = order[p];
+    if (g < 0 || g >= gaps || lo[g] < 0) return;
+    const int f = (int)(keys[g] >> RAHT_FRAME_BIT);
+    const int64_t w1 = g - lo[g] + 1, w2 = hi[g] - g;
+    int32_t z[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        int32_t t = tokens[3 * p + c];
+        t = t < 0 ? 0 : (t > RAHT_ESCAPE ? RAHT_ESCAPE : t);
+        if (t == RAHT_ESCAPE) { const int64_t e = prefix[3 * p + c]; t += e < n_esc ? (esc[e] & 1023) : 0; }
+        z[c] = t;
+    }
+    const int64_t dl = delta16(q.luma[f], w1, w2), dc = delta16(q.chroma[f], w1, w2);
+    Hhat[g] = i3{dequant(z[0], dl), dequant(z[1], dc), dequant(z[2], dc)};
+}
+extern "C" int64_t pcgc_raht_dequantize_batch_workspace_bytes(int64_t n, int frames) {
+    const size_t t = tokens_of_batch(n, frames);
+    return (int64_t)(align256(t) + align256(t * 4) + align256(pcgc_scan_workspace_bytes((int64_t)t)));
+}
+extern "C" int pcgc_raht_dequantize_batch(const int16_t* tokens, const uint16_t* escapes, int64_t n_escapes, int64_t n, int frames,
+                                          const uint64_t* keys, const int32_t* lo, const int32_t* hi, const int32_t* order, const int32_t* q_luma,
+                                          const int32_t* q_chroma, int32_t* Hhat, int32_t* n_escape_tokens, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+    PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
+    PCGC_REQUIRE(frames >= 1 && frames <= RAHT_MAX_FRAMES && frames <= n, "1 to 16 frames of at least one point");
+    PCGC_REQUIRE(q_luma && q_chroma && n_escapes >= 0 && n_escape_tokens && workspace, "bad argument");
+    RahtSteps q;
+    PCGC_REQUIRE(steps_of(q_luma, q_chroma, frames, q), "quantiser 0 .. 255");
+    PCGC_REQUIRE(workspace_bytes >= (size_t)pcgc_raht_dequantize_batch_workspace_bytes(n, frames), "workspace too small");
+    hipError_t e = hipMemsetAsync(n_escape_tokens, 0, (RAHT_MAX_FRAMES + 1) * sizeof(int32_t), S(stream));
+    if (e != hipSuccess) { pcgc_set_error("raht_dequantize_batch: %s", hipGetErrorString(e)); return -1; }
+    if (n == frames) return 0;
+    PCGC_REQUIRE(tokens && keys && lo && hi && order && Hhat && (n_escapes == 0 || escapes), "null argument");
+    const int64_t coded = n - frames, t = 3 * coded;
+    char* ws = (char*)workspace;
+    uint8_t* escmask = (uint8_t*)ws; ws += align256((size_t)t);
+    int32_t* prefix = (int32_t*)ws; ws += align256((size_t)t * 4);
+    hipLaunchKernelGGL(k_raht_escmask_batch, dim3(grid_for(t, 256)), dim3(256), 0, S(stream), tokens, t, order, keys, n - 1, escmask, n_escape_tokens);
+    PCGC_CHECK_LAUNCH("raht_dequantize_batch");
+    if (pcgc_mask_scan(escmask, t, prefix, n_escape_tokens + RAHT_MAX_FRAMES, ws, pcgc_scan_workspace_bytes(t), stream) != 0) return -1;
+    hipLaunchKernelGGL(k_raht_dequantize_batch, dim3(grid_for(coded, 256)), dim3(256), 0, S(stream), tokens, prefix, escapes, n_escapes, coded, n - 1,
+                       keys, lo, hi, order, q, (i3*)Hhat);
+    PCGC_CHECK_LAUNCH("raht_dequantize_batch");
     return 0;
 }

@@ -1784,6 +1784,165 @@ def raht_inverse(tree, Hhat, dc, form=None):
     return rgb
 
 
+# ------------------------------------------------------------------------------------------------ colour transform, a batch of frames
+RAHT_MAX_FRAMES = 16
+
+
+class RahtBatchTree(RahtTree):
+    """The trees of B frames from one key build, one sort and one tree build (pcgc_raht_keys_batch + pcgc_raht_tree_batch).  Sorted leaves
+    [starts[b], starts[b + 1]) are frame b; gap arrays are indexed by the batch's gaps, a frame boundary has lo = hi = -1.  order: the
+    n - B merges in coding order, frame by frame (frame b's are positions [starts[b] - b, starts[b + 1] - b - 1)), then the boundaries.
+    bucket: int32 [B,65] on the host, row b the offsets of frame b alone; offsets: [(B + 1) x 65] on the device, the last row = cross.
+    bit_off: int32 [130] on the host, for the form that launches per split bit (include/pcgc_hip.h)."""
+    __slots__ = ('frames', 'starts', 'starts_dev', 'bit_off')
+
+    @property
+    def tok(self):
+        """int64 [B + 1]: frame b's tokens are [tok[b], tok[b + 1]) of the batch's coding order"""
+        return 3 * (self.starts - np.arange(self.frames + 1))
+
+
+def raht_tree_batch(coords, frames, times=None):
+    """coords int32 [n,4] rows (b, x, y, z), b in 0 .. frames - 1 and x, y, z in [0, 2^20), in any order -> RahtBatchTree.  ValueError for
+    frames outside 1 .. 16, a frame index outside 0 .. frames - 1 or without rows, coordinates out of range, duplicates within a frame (the
+    frame is named), an empty batch or more than 2^24 rows."""
+    import time
+    coords = _i32(coords)
+    if coords.dim() != 2 or coords.shape[1] != 4:
+        raise ValueError(f'raht_tree_batch: coordinates must be [n,4], got {tuple(coords.shape)}')
+    n, dev, B = coords.shape[0], coords.device, int(frames)
+    if not 1 <= B <= RAHT_MAX_FRAMES:
+        raise ValueError(f'raht_tree_batch: {B} frames; a batch holds 1 .. {RAHT_MAX_FRAMES}')
+    if not 1 <= n <= RAHT_MAX_POINTS:
+        raise ValueError(f'raht_tree_batch: {n} rows; the colour transform takes 1 .. 2^24 in a batch')
+    t = RahtBatchTree()
+    t.n, t.device, t.frames = n, dev, B
+    g = max(n - 1, 1)
+    t.keys = torch.empty(n, dtype=torch.int64, device=dev)
+    t.perm = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(34, dtype=torch.int32, device=dev)
+    ws_bytes = max(int(lib().pcgc_raht_keys_batch_workspace_bytes(n)), int(lib().pcgc_raht_tree_batch_workspace_bytes(n)))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    s = _stream(coords)
+
+    def tick(phase, t0):
+        if times is None:
+            return 0.0
+        torch.cuda.synchronize(dev)
+        now = time.perf_counter()
+        if phase is not None:
+            times[phase] = times.get(phase, 0.0) + now - t0
+        return now
+
+    t0 = tick(None, 0.0)
+    check(lib().pcgc_raht_keys_batch(_p(coords), n, B, _p(t.keys), _p(t.perm), _p(status), _p(ws), ws_bytes, s), 'raht_keys_batch')
+    t0 = tick('keys + sort', t0)
+    t.d = torch.empty(g, dtype=torch.uint8, device=dev)[:n - 1]
+    t.lo, t.hi, t.left, t.right, t.order, t.cross_order = (torch.empty(g, dtype=torch.int32, device=dev)[:n - 1] for _ in range(6))
+    t.offsets = torch.empty((B + 1) * 65, dtype=torch.int32, device=dev)
+    check(lib().pcgc_raht_tree_batch(_p(t.keys), n, B, _p(t.d), _p(t.lo), _p(t.hi), _p(t.left), _p(t.right), _p(t.order), _p(t.cross_order),
+                                     _p(t.offsets), _p(ws), ws_bytes, s), 'raht_tree_batch')
+    status = status.cpu().numpy()
+    dups, rows, flags = status[:B], status[16:16 + B].astype(np.int64), int(status[32])
+    if flags & 2:
+        raise ValueError(f'raht_tree_batch: rows with a frame index outside 0 .. {B - 1}')
+    if flags & 1:
+        raise ValueError('raht_tree_batch: coordinates outside [0, 2^20)')
+    if (rows == 0).any():
+        raise ValueError(f'raht_tree_batch: frame {int(np.flatnonzero(rows == 0)[0])} has no rows; every frame of a batch needs at least one')
+    if dups.any():
+        b = int(np.flatnonzero(dups)[0])
+        raise ValueError(f'raht_tree_batch: frame {b} has {int(dups[b])} duplicate voxels; the colour transform needs distinct voxels')
+    off = t.offsets.cpu().numpy().reshape(B + 1, 65)
+    tick('tree', t0)
+    t.bucket, t.cross = np.ascontiguousarray(off[:B]), np.ascontiguousarray(off[B])
+    t.starts = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+    t.starts_dev = torch.from_numpy(t.starts[:B].astype(np.int32)).to(dev)
+    rest = np.diff(t.bucket.astype(np.int64), axis=1).sum(0) - np.diff(t.cross.astype(np.int64))      # merges per bucket that cross no tile
+    t.bit_off = np.ascontiguousarray(np.concatenate([t.cross, t.cross[64] + np.concatenate([[0], np.cumsum(rest)])]), dtype=np.int32)
+    return t
+
+
+def _frame_steps(tree, q_luma, q_chroma):
+    ql, qc = np.ascontiguousarray(q_luma, dtype=np.int32), np.ascontiguousarray(q_chroma, dtype=np.int32)
+    if ql.shape != (tree.frames,) or qc.shape != (tree.frames,):
+        raise ValueError(f'quantiser steps per frame: two sequences of {tree.frames}, got {ql.shape} and {qc.shape}')
+    return ql, qc
+
+
+def raht_forward_batch(tree, rgb, form=None):
+    """rgb uint8 [n,3] in the row order of the batch's coordinates -> (H int32 [n-1,3] per gap of the batch (a frame boundary's row is not
+    written), DC int32 [B,3] on the device); one transform for all frames"""
+    rgb = _u8(rgb, 'raht_forward_batch: colours')
+    if rgb.dim() != 2 or tuple(rgb.shape) != (tree.n, 3):
+        raise ValueError(f'raht_forward_batch: colours must be [{tree.n},3], got {tuple(rgb.shape)}')
+    val = torch.empty((tree.n, 3), dtype=torch.int32, device=tree.device)
+    H = torch.empty((max(tree.n - 1, 1), 3), dtype=torch.int32, device=tree.device)[:tree.n - 1]
+    check(lib().pcgc_raht_forward_batch(_p(rgb), _p(tree.perm), tree.n, _p(tree.d), _p(tree.lo), _p(tree.hi), _p(tree.cross_order),
+                                        tree.bit_off.ctypes.data, _p(tree.offsets) + tree.frames * 65 * 4, _raht_form(form), _p(val), _p(H),
+                                        _stream(rgb)), 'raht_forward_batch')
+    return H, val.index_select(0, tree.starts_dev)
+
+
+def raht_quantize_batch(tree, H, q_luma, q_chroma):
+    """q_luma, q_chroma: B ints each -> (tokens int16 [3(n-B)], ctx [3(n-B)], escapes [E], hist int32 [B,48,64]) on the device in the
+    batch's coding order: frame b's tokens are tree.tok[b] .. tree.tok[b + 1], its escapes follow those of the frames before it and are
+    hist[b, :, 63].sum() many"""
+    n, dev, B = tree.n, tree.device, tree.frames
+    ql, qc = _frame_steps(tree, q_luma, q_chroma)
+    t = max(3 * (n - B), 1)
+    tokens = torch.empty(t, dtype=torch.int16, device=dev)[:3 * (n - B)]
+    ctx = torch.empty(t, dtype=torch.int16, device=dev)[:3 * (n - B)]
+    esc = torch.empty(t, dtype=torch.int16, device=dev)
+    n_esc = torch.empty(1, dtype=torch.int32, device=dev)
+    hist = torch.empty((B, RAHT_CONTEXTS, 64), dtype=torch.int32, device=dev)
+    ws_bytes = int(lib().pcgc_raht_quantize_batch_workspace_bytes(n, B))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    check(lib().pcgc_raht_quantize_batch(_p(_dev(H, torch.int32, 'raht_quantize_batch: H')), n, B, _p(tree.keys), _p(tree.d), _p(tree.lo),
+                                         _p(tree.hi), _p(tree.order), ql.ctypes.data, qc.ctypes.data, _p(tokens), _p(ctx), _p(esc), _p(n_esc),
+                                         _p(hist), _p(ws), ws_bytes, _stream(H)), 'raht_quantize_batch')
+    return tokens, ctx, esc, hist
+
+
+def raht_dequantize_batch(tree, tokens, escapes, esc_counts, q_luma, q_chroma):
+    """tokens int16 [3(n-B)] and the frames' escape lists one after the other (int16 storage) on the device, esc_counts: the length of
+    each list -> H^ int32 [n-1,3].  PcgcError naming the frame whose number of escape tokens is not the length of its list."""
+    n, dev, B = tree.n, tree.device, tree.frames
+    ql, qc = _frame_steps(tree, q_luma, q_chroma)
+    if tokens.shape[0] != 3 * (n - B):
+        raise PcgcError(f'raht_dequantize_batch: {tokens.shape[0]} tokens for {n} points in {B} frames')
+    Hhat = torch.empty((max(n - 1, 1), 3), dtype=torch.int32, device=dev)[:n - 1]
+    count = torch.empty(17, dtype=torch.int32, device=dev)
+    ws_bytes = int(lib().pcgc_raht_dequantize_batch_workspace_bytes(n, B))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    tokens, escapes = _dev(tokens, torch.int16, 'raht_dequantize_batch: tokens'), _dev(escapes, torch.int16, 'raht_dequantize_batch: escapes')
+    check(lib().pcgc_raht_dequantize_batch(_p(tokens), _p(escapes) if escapes.shape[0] else None, escapes.shape[0], n, B, _p(tree.keys),
+                                           _p(tree.lo), _p(tree.hi), _p(tree.order), ql.ctypes.data, qc.ctypes.data, _p(Hhat), _p(count), _p(ws),
+                                           ws_bytes, _stream(tokens)), 'raht_dequantize_batch')
+    count = count.cpu().tolist()
+    for b in range(B):
+        if count[b] != int(esc_counts[b]):
+            raise PcgcError(f'raht_dequantize_batch: frame {b}: {count[b]} escape tokens but {int(esc_counts[b])} escapes')
+    return Hhat
+
+
+def raht_inverse_batch(tree, Hhat, dc, form=None):
+    """H^ int32 [n-1,3] and the frames' DCs ([B,3] ints) -> rgb uint8 [n,3] in the row order of the batch's coordinates"""
+    val = torch.empty((tree.n, 3), dtype=torch.int32, device=tree.device)
+    rgb = torch.empty((tree.n, 3), dtype=torch.uint8, device=tree.device)
+    if tuple(Hhat.shape) != (tree.n - 1, 3):
+        raise ValueError(f'raht_inverse_batch: H^ must be [{tree.n - 1},3], got {tuple(Hhat.shape)}')
+    dc = np.ascontiguousarray(dc, dtype=np.int32)
+    if dc.shape != (tree.frames, 3):
+        raise ValueError(f'raht_inverse_batch: the DCs must be [{tree.frames},3], got {dc.shape}')
+    dc = torch.from_numpy(dc).to(tree.device)
+    check(lib().pcgc_raht_inverse_batch(_p(_dev(Hhat, torch.int32, 'raht_inverse_batch: H^')), _p(dc), _p(tree.starts_dev), tree.frames,
+                                        _p(tree.perm), tree.n, _p(tree.d), _p(tree.lo), _p(tree.hi), _p(tree.cross_order),
+                                        tree.bit_off.ctypes.data, _p(tree.offsets) + tree.frames * 65 * 4, _raht_form(form), _p(val), _p(rgb),
+                                        _stream(Hhat)), 'raht_inverse_batch')
+    return rgb
+
+
 # ------------------------------------------------------------------------------------------------ colour codec, device coder (csrc/attribute_rans.hip)
 def attr_rans_chunks(n, steps):
     """chunks of 64 x steps tokens that n tokens make"""
@@ -1869,6 +2028,105 @@ def attr_rans_decode(table, tree, payload, n):
         raise PcgcError(f'attr_rans_decode: unsound payload ({int(host[1])} of {chunks} chunks fail their check: states in [2^31, 2^63), '
                         'exactly W_k words consumed, every lane back at 2^31)')
     return tokens, int(host[0])
+
+
+def attr_rans_batch_layout(tokens_per_frame, chunk_steps):
+    """How a batch's frames are cut into chunks and where their payloads stand in one device buffer.  tokens_per_frame: B token counts;
+    chunk_steps: steps per chunk for every frame (0: each frame is one chunk with its own S_b = ceil(n_b / 64)), or B values ->
+    {steps [B] (0 for a frame without tokens), chunks [B], first_chunk [B + 1], tok [B + 1], room [B] (8 + 516 K_b + 4 n_b, 0 without
+    tokens), pay [B + 1] (byte offsets, multiples of 8)}, all int64 except steps (int32).  Chunks never straddle frames."""
+    counts = np.asarray(tokens_per_frame, dtype=np.int64).reshape(-1)
+    want = np.broadcast_to(np.asarray(chunk_steps, dtype=np.int64), counts.shape)
+    if (counts < 0).any() or (want < 0).any() or (want > RANS_MAX_STEPS).any():
+        raise ValueError(f'attr_rans_batch_layout: token counts {counts.tolist()}, steps per chunk {want.tolist()} (0 .. 2^24)')
+    steps = np.where(counts > 0, np.where(want > 0, want, -(-counts // RANS_LANES)), 0)
+    chunks = np.where(counts > 0, -(-counts // (RANS_LANES * np.maximum(steps, 1))), 0)
+    room = np.where(counts > 0, 8 + 516 * chunks + 4 * counts, 0)
+    edge = lambda v: np.concatenate([[0], np.cumsum(v)]).astype(np.int64)
+    return {'steps': steps.astype(np.int32), 'chunks': chunks, 'first_chunk': edge(chunks), 'tok': edge(counts), 'room': room,
+            'pay': edge((room + 7) // 8 * 8)}
+
+
+def _attr_tables(tables, frames, dev):
+    tables = np.ascontiguousarray(tables, dtype=np.uint16)
+    if tables.shape != (frames, RAHT_CONTEXTS, 65):
+        raise PcgcError(f'attr_rans: the tables of a batch are uint16 [{frames}, {RAHT_CONTEXTS}, 65], got {tables.shape}')
+    return torch.from_numpy(tables.view(np.int16)).to(dev)
+
+
+def attr_rans_encode_batch(tables, ctx, tokens, tok, chunk_steps):
+    """tables uint16 [B,48,65] (host), ctx and tokens [n] on the device as raht_quantize_batch returns them, tok [B + 1]: frame b's tokens
+    are tok[b] .. tok[b + 1] -> B payloads (bytes; b'' for a frame without tokens), every one what attr_rans_encode gives for that frame
+    alone at its own steps per chunk.  ONE launch sequence, one small synchronising copy and one copy of the payloads for the batch; a batch
+    without tokens launches nothing.  PcgcError naming the frame with a token that cannot be coded."""
+    tok = np.ascontiguousarray(tok, dtype=np.int64)
+    B, n, dev = tok.size - 1, int(tok[-1]), tokens.device
+    if _dev(tokens, torch.int16, 'attr_rans_encode_batch: tokens').dim() != 1 or tuple(_dev(ctx, torch.int16, 'attr_rans_encode_batch: ctx').shape) \
+            != (n,) or tokens.shape[0] != n or not 1 <= B <= RAHT_MAX_FRAMES:
+        raise PcgcError(f'attr_rans_encode_batch: tokens {tuple(tokens.shape)}, ctx {tuple(ctx.shape)}, {B} frames of {n} tokens')
+    lay = attr_rans_batch_layout(np.diff(tok), chunk_steps)
+    tables = _attr_tables(tables, B, dev)
+    if n == 0:
+        return [b''] * B
+    pay, K = lay['pay'], int(lay['first_chunk'][-1])
+    out = torch.empty(int(pay[-1]) // 8, dtype=torch.int64, device=dev)
+    nbytes = int(lib().pcgc_attr_rans_batch_workspace_bytes(n, K))
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    host = np.zeros(2 * B, dtype=np.int64)
+    check(lib().pcgc_attr_rans_encode_batch(_p(tables), _p(ctx), _p(tokens), B, tok.ctypes.data, lay['steps'].ctypes.data, _p(out), pay.ctypes.data,
+                                            host.ctypes.data, _p(ws), nbytes, _stream(tokens)), 'attr_rans_encode_batch')
+    for b in range(B):
+        if host[B + b]:
+            raise PcgcError(f'attr_rans_encode_batch: frame {b}: {int(host[B + b])} tokens cannot be coded (outside 0 .. 63, under a context '
+                            'outside 0 .. 47, or of frequency 0 in their row)')
+    raw = out.view(torch.uint8)
+    down = torch.cat([raw[int(pay[b]):int(pay[b]) + int(host[b])] for b in range(B)]).cpu().numpy().tobytes()      # the finished payloads, one copy
+    edge = np.concatenate([[0], np.cumsum(host[:B])])
+    return [down[int(edge[b]):int(edge[b + 1])] for b in range(B)]
+
+
+def attr_rans_decode_batch(tables, tree, payloads, tokens=None, names=None):
+    """tables uint16 [B,48,65] (host), tree: the RahtBatchTree, payloads: per frame the bytes of a version-2 payload, or None for a frame
+    that is not decoded here (its slice of the result is left unwritten) -> (tokens int16 [3(n-B)] on the device in the batch's coding
+    order, the tokens that are 63 per frame).  Every payload's S, K and lengths are checked here before any launch; one upload, ONE launch
+    sequence and one small copy for the batch.  tokens: the int16 [3(n-B)] device tensor to write the decoded frames' slices into (the
+    others keep what they hold).  PcgcError naming the frame (names[b], else 'frame b') of a bad head or an unsound chunk."""
+    B, dev, tok = tree.frames, tree.offsets.device, np.ascontiguousarray(tree.tok, dtype=np.int64)
+    if len(payloads) != B:
+        raise PcgcError(f'attr_rans_decode_batch: {len(payloads)} payloads for {B} frames')
+    names = [f'frame {b}' for b in range(B)] if names is None else list(names)
+    steps, pay, size, blob = np.zeros(B, np.int32), np.zeros(B, np.int64), np.zeros(B, np.int64), bytearray()
+    for b, payload in enumerate(payloads):
+        if payload is None:
+            continue
+        try:
+            steps[b], _ = attr_rans_layout(payload, int(tok[b + 1] - tok[b]))
+        except PcgcError as e:
+            raise PcgcError(f'{names[b]}: {e}') from None
+        pay[b], size[b] = len(blob), len(payload)
+        blob += bytes(payload) + bytes(-len(payload) % 8)
+    tables = _attr_tables(tables, B, dev)
+    n = int(tok[-1])
+    if tokens is None:
+        tokens = torch.empty(max(n, 1), dtype=torch.int16, device=dev)[:n]
+    elif tuple(_dev(tokens, torch.int16, 'attr_rans_decode_batch: tokens').shape) != (n,):
+        raise PcgcError(f'attr_rans_decode_batch: a token buffer of {tuple(tokens.shape)} for {n} tokens')
+    escapes = np.zeros(B, np.int64)
+    if not steps.any():
+        return tokens, escapes
+    K = int(sum(attr_rans_chunks(tok[b + 1] - tok[b], steps[b]) for b in range(B) if steps[b]))
+    up = torch.frombuffer(blob, dtype=torch.int64).to(dev)
+    nbytes = int(lib().pcgc_attr_rans_batch_workspace_bytes(n, K))
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    host = np.zeros(2 * B, dtype=np.int64)
+    check(lib().pcgc_attr_rans_decode_batch(_p(tables), _p(tree.offsets), B, tok.ctypes.data, steps.ctypes.data, _p(up), pay.ctypes.data,
+                                            size.ctypes.data, _p(tokens), host.ctypes.data, _p(ws), nbytes, _stream(tokens)),
+          'attr_rans_decode_batch')
+    for b in range(B):
+        if host[B + b]:
+            raise PcgcError(f'{names[b]}: attr_rans_decode_batch: unsound payload ({int(host[B + b])} chunks fail their check: states in '
+                            '[2^31, 2^63), exactly W_k words consumed, every lane back at 2^31)')
+    return tokens, host[:B].copy()
 
 
 # ------------------------------------------------------------------------------------------------ estimated normals (csrc/normals.hip)

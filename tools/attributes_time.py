@@ -9,7 +9,11 @@ colours onto the decoded cloud (shared and own searches) and the lossy geometry 
 With --attribute_coder device it times the device coder of `_A.bin` version 2 instead: version 1 first, then per value of
 --chunk_steps the chunks, the bits of `_A.bin` and their excess over version 1, encode and decode as whole calls and the synchronised time
 of the coder phase, all in this one process, the decoded colours compared with version 1's.
-    tools/attributes_time.py --attribute_coder device [--chunk_steps 1024,4096,16384,0] [--cloud NAME] [--qstep Q] [--repeat K]"""
+    tools/attributes_time.py --attribute_coder device [--chunk_steps 1024,4096,16384,0] [--cloud NAME] [--qstep Q] [--repeat K]
+With --batch B it times ONE encode_batch + decode_batch of B copies of the cloud (the noise of the colour field drawn with another seed per
+copy, so the streams differ) against B frame-by-frame encode + decode calls, in this one process: the median per phase of
+both, the bits of every file, and whether the batch wrote the same bytes and decoded the same colours.
+    tools/attributes_time.py --batch B [--attribute_coder device] [--cloud NAME] [--qstep Q] [--repeat K]"""
 import argparse, csv, glob, json, os, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -22,6 +26,7 @@ ap.add_argument('--no-host', action='store_true', help='skip the numpy definitio
 ap.add_argument('--trace', action='store_true', help='also one rocprofv3 --kernel-trace --stats run of two calls per form (child process)')
 ap.add_argument('--attribute_coder', choices=('host', 'device'), default='host', help='device: time the device coder over --chunk_steps instead')
 ap.add_argument('--chunk_steps', default='1024,4096,16384,0', help='with --attribute_coder device: steps per chunk, comma separated (0: one chunk)')
+ap.add_argument('--batch', type=int, default=0, help='time encode_batch / decode_batch of this many copies against frame-by-frame calls')
 ap.add_argument('--one-call', action='store_true', help=argparse.SUPPRESS)
 args = ap.parse_args()
 
@@ -92,6 +97,42 @@ def phases(fn, coder):
     out['whole call, no stopwatch'] = median_ms(fn)
     return out
 
+
+if args.batch:
+    from pcgcv2_amd.attributes import CHUNK_STEPS
+    B = args.batch
+    noise = lambda seed: torch.randint(-12, 13, rgb.shape, device=dev, generator=torch.Generator(device=dev).manual_seed(seed))
+    colours = [(rgb + noise(1 + b)).round().clamp(0, 255).to(torch.uint8) for b in range(B)]
+    frames = [torch.cat([torch.full((len(pts), 1), b, dtype=torch.int32, device=dev), pts], 1) for b in range(B)]
+    shuffle = torch.randperm(B * len(pts), device=dev, generator=torch.Generator(device=dev).manual_seed(7))       # frames interleaved
+    a_all, c_all = torch.cat(frames)[shuffle].contiguous(), torch.cat(colours)[shuffle].contiguous()
+    postfixes = [f'_{b}' for b in range(B)]
+    single = AttributeCoder(prefix + 's', attribute_coder=args.attribute_coder)
+    batch = AttributeCoder(prefix + 'b', attribute_coder=args.attribute_coder)
+
+    def single_encode():
+        for b in range(B):
+            single.encode(a, colours[b], args.qstep, postfix=postfixes[b])
+
+    def single_decode():
+        return [single.decode(a, postfix=postfixes[b]) for b in range(B)]
+
+    report = {'cloud': args.cloud, 'frames': B, 'points_per_frame': len(a), 'qstep': args.qstep, 'runs': runs, 'form': ops.RAHT_FORM,
+              'attribute_coder': args.attribute_coder, 'chunk_steps': CHUNK_STEPS,
+              'frame_by_frame_ms': {'encode': phases(single_encode, single), 'decode': phases(single_decode, single)},
+              'batch_ms': {'encode': phases(lambda: batch.encode_batch(a_all, c_all, args.qstep, postfixes=postfixes), batch),
+                           'decode': phases(lambda: batch.decode_batch(a_all, postfixes=postfixes), batch)}}
+    report['bits_A'] = {'frame_by_frame': [8 * os.path.getsize(prefix + 's' + p + '_A.bin') for p in postfixes],
+                        'batch': [8 * os.path.getsize(prefix + 'b' + p + '_A.bin') for p in postfixes]}
+    report['same_bytes'] = all(open(prefix + 's' + p + '_A.bin', 'rb').read() == open(prefix + 'b' + p + '_A.bin', 'rb').read() for p in postfixes)
+    got, want = batch.decode_batch(a_all, postfixes=postfixes), single_decode()
+    back = torch.empty_like(got)
+    back[shuffle] = got                                               # row b len(pts) + i: frame b's row i
+    report['same_colours'] = all(bool(torch.equal(back[b * len(pts):(b + 1) * len(pts)], want[b])) for b in range(B))
+    whole = lambda side, kind: report[kind][side]['whole call, no stopwatch']
+    report['speedup'] = {side: round(whole(side, 'frame_by_frame_ms') / whole(side, 'batch_ms'), 3) for side in ('encode', 'decode')}
+    print(json.dumps(report, indent=1))
+    raise SystemExit(0)
 
 if args.attribute_coder == 'device':
     from pcgcv2_amd.attributes import CHUNK_STEPS
