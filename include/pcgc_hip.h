@@ -617,7 +617,8 @@ int pcgc_raht_dequantize(const int16_t* tokens, const uint16_t* escapes, int64_t
  *      2^24 rows in all.  The frame index is bits 60 .. 63 of the key (compared unsigned), so after one sort frame b is the run of leaves
  *      [start_b, start_b + n_b); a gap with d < 60 lies inside one frame and has there the lo, hi and children it has in that frame alone,
  *      shifted by start_b.  The B - 1 gaps with d >= 60 are frame boundaries: no merge, no token, lo = hi = -1.  Every output of frame b is
- *      what the single-frame entries above give for its rows alone. ---- */
+ *      what the single-frame entries above give for its rows alone: a single frame is the batch of one, and the entries above run the
+ *      kernels and host bodies of the entries below at frames = 1 (likewise pcgc_attr_rans_encode / _decode and their _batch entries). ---- */
 /* status [34] (dev): [0 .. 15] adjacent equal keys per frame (the same voxel in two frames is no duplicate), [16 .. 31] rows per frame,
  * [32] bit 0 = a coordinate outside [0, 2^20), bit 1 = a frame index outside 0 .. frames - 1. */
 int64_t pcgc_raht_keys_batch_workspace_bytes(int64_t n);

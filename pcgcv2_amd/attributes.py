@@ -28,7 +28,6 @@ AttributeCoder.encode_batch / decode_batch code up to 16 frames in one pass over
 """
 import os
 import struct
-import time
 
 import numpy as np
 import torch
@@ -74,6 +73,14 @@ def contexts(bucket):
 def _pack_escapes(esc):
     bits = ((np.asarray(esc, np.uint16)[:, None] >> np.arange(ESCAPE_BITS, dtype=np.uint16)) & 1).astype(np.uint8).reshape(-1)
     return np.packbits(bits, bitorder='little').tobytes()
+
+
+def _container(version, n, ql, qc, dc, rows, table, n_tok, payload, esc):
+    """the bytes of one `_A.bin`: head, the table rows of the contexts that occur, sizes, payload, escapes, CRC"""
+    blob = _HEAD.pack(MAGIC, version, n, ql, qc, dc[0], dc[1], dc[2], len(rows))
+    blob += b''.join(struct.pack('<H', c) + table[c, 1:TOKENS].astype('<u2').tobytes() for c in rows)
+    blob += _SIZES.pack(n_tok, len(payload), esc.size) + payload + _pack_escapes(esc)
+    return blob + struct.pack('<I', ops.crc32(blob))
 
 
 def _unpack_escapes(data, count):
@@ -186,14 +193,7 @@ class AttributeCoder():
         self.times = None                         # measurement hook (tools/attributes_time.py): a dict -> seconds per phase, synchronised
 
     def _tick(self, phase, t0, dev=None):
-        if self.times is None:
-            return 0.0
-        if dev is not None:
-            torch.cuda.synchronize(dev)
-        now = time.perf_counter()
-        if phase is not None:
-            self.times[phase] = self.times.get(phase, 0.0) + now - t0
-        return now
+        return ops.tick_phase(self.times, phase, t0, dev)
 
     @staticmethod
     def _coords(coords):
@@ -240,10 +240,7 @@ class AttributeCoder():
                 t = self._tick('device coder', t, dev)
             else:
                 payload = ops.rc_encode_ctx(table, ctx_h, tokens_h) if n_tok else b''
-            blob = _HEAD.pack(MAGIC, CODERS[self.attribute_coder], tree.n, ql, qc, dc_h[0], dc_h[1], dc_h[2], len(rows))
-            blob += b''.join(struct.pack('<H', c) + table[c, 1:TOKENS].astype('<u2').tobytes() for c in rows)
-            blob += _SIZES.pack(n_tok, len(payload), esc_h.size) + payload + _pack_escapes(esc_h)
-            blob += struct.pack('<I', ops.crc32(blob))
+            blob = _container(CODERS[self.attribute_coder], tree.n, ql, qc, dc_h, rows, table, n_tok, payload, esc_h)
             _dump(self.filename + postfix + SUFFIX, blob)
             self._tick('host coder', t)
         return {'bits_A': 8 * len(blob), 'tokens': n_tok, 'escapes': int(esc_h.size), 'payload_bytes': len(payload), 'tree': tree}
@@ -355,10 +352,7 @@ class AttributeCoder():
             records = []
             for b in range(B):
                 (rows, table), n_tok, e = made[b], int(tok[b + 1] - tok[b]), esc_h[esc_at[b]:esc_at[b + 1]]
-                blob = _HEAD.pack(MAGIC, CODERS[self.attribute_coder], n_tok // 3 + 1, ql[b], qc[b], dc_h[b][0], dc_h[b][1], dc_h[b][2], len(rows))
-                blob += b''.join(struct.pack('<H', c) + table[c, 1:TOKENS].astype('<u2').tobytes() for c in rows)
-                blob += _SIZES.pack(n_tok, len(payloads[b]), e.size) + payloads[b] + _pack_escapes(e)
-                blob += struct.pack('<I', ops.crc32(blob))
+                blob = _container(CODERS[self.attribute_coder], n_tok // 3 + 1, ql[b], qc[b], dc_h[b], rows, table, n_tok, payloads[b], e)
                 _dump(self.filename + postfixes[b] + SUFFIX, blob)
                 records.append({'bits_A': 8 * len(blob), 'tokens': n_tok, 'escapes': int(e.size), 'payload_bytes': len(payloads[b])})
             self._tick('host coder', t)

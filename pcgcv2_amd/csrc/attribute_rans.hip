@@ -20,8 +20,10 @@
 //            memory and the token is in 0 .. 63 whatever the table says.  Words are staged through a ring in LDS as in occupancy_rans.hip.
 //            The contexts come from k_attr_rans_ctx, which derives them from the tree's bucket offsets: they are never uploaded.
 //
-// A batch of frames (pcgc_attr_rans_*_batch) is one launch of the chunks of all frames: the chunk bodies below are shared, a
-// workgroup serves one frame's chunk with that frame's table, and every frame's payload is packed on its own.
+// A batch of frames (pcgc_attr_rans_*_batch) is one launch of the chunks of all frames: a workgroup serves one frame's chunk
+// with that frame's table, and every frame's payload is packed on its own.  A SINGLE FRAME IS THE BATCH OF ONE: there is one kernel per step
+// (encode, offsets, compact, contexts, decode) over an ArFrames, one workspace layout and one pinned slot; pcgc_attr_rans_encode / _decode
+// build the ArFrames of one frame (of any length: only the batch entries demand token counts in multiples of 3) and run the same bodies.
 //
 // No workgroup reads what another wrote in the same launch.  All integer arithmetic: the bytes are a function of the input alone.
 #include <cstring>
@@ -124,19 +126,9 @@ __device__ __forceinline__ void ar_encode_chunk(const uint32_t* sh, const uint16
     for (int d = 32; d > 0; d >>= 1) bad += __shfl_xor(bad, d, 64);
     if (lane == 0 && bad) atomicAdd(refused, (unsigned long long)bad);           // (integer atomic: the sum does not depend on the order)
 }
-__global__ void __launch_bounds__(AR_LANES) k_attr_rans_encode(const uint16_t* __restrict__ table, const uint16_t* __restrict__ ctx,
-                                                               const int16_t* __restrict__ tokens, int64_t n, int S, uint32_t* __restrict__ scratch,
-                                                               unsigned long long* __restrict__ states, uint32_t* __restrict__ wcount,
-                                                               unsigned long long* __restrict__ refused) {
-    __shared__ __attribute__((aligned(16))) uint32_t sh[AR_CONTEXTS * AR_ROW];
-    ar_load_table(sh, table);
-    const int64_t k = blockIdx.x, base = k * AR_LANES * S;
-    const int rows = (int)(n - base < (int64_t)AR_LANES * S ? n - base : (int64_t)AR_LANES * S);
-    ar_encode_chunk(sh, ctx + base, tokens + base, rows, scratch + base, states + k * AR_LANES, wcount + k, refused);
-}
-
-// A batch of frames in ONE launch sequence (pcgc_attr_rans_*_batch): chunks never straddle frames, so a workgroup serves one frame and loads
-// that frame's table.  The table below travels by value; chunk k of the launch belongs to the last frame f with chunk[f] <= k.
+// A batch of frames in ONE launch sequence; a single frame is the batch of one (frames = 1, tok = {0, n}, pay = {0}).  Chunks never straddle
+// frames, so a workgroup serves one frame and loads that frame's table.  The table below travels by value; chunk k of the launch belongs to
+// the last frame f with chunk[f] <= k.
 constexpr int AR_MAX_FRAMES = 16;
 struct ArFrames {
     long long tok[AR_MAX_FRAMES + 1];          // first token of the frame in the batch's coding order; tok[frames] = all tokens
@@ -151,25 +143,43 @@ __device__ static inline int ar_frame_of(const ArFrames& fr, int64_t k) {
     for (int b = 1; b < AR_MAX_FRAMES; ++b) f += (b < fr.frames && (int64_t)fr.chunk[b] <= k) ? 1 : 0;     // (chunk[] ascends)
     return f;
 }
-__global__ void __launch_bounds__(AR_LANES) k_attr_rans_encode_batch(const uint16_t* __restrict__ tables, const uint16_t* __restrict__ ctx,
-                                                                     const int16_t* __restrict__ tokens, ArFrames fr, uint32_t* __restrict__ scratch,
-                                                                     uint8_t* __restrict__ payload, unsigned long long* __restrict__ refused) {
+// chunk blockIdx.x of the launch: its frame f, the frame's S, K and tokens, the chunk's place k in the frame, its first token and its rows
+struct ArChunk { int f, S, rows; int64_t k, K, base; };
+__device__ static inline ArChunk ar_chunk_of(const ArFrames& fr) {
+    ArChunk c;
+    c.f = ar_frame_of(fr, blockIdx.x);
+    c.S = fr.steps[c.f];
+    c.k = (int64_t)blockIdx.x - fr.chunk[c.f];
+    c.K = fr.chunk[c.f + 1] - fr.chunk[c.f];
+    const int64_t n = fr.tok[c.f + 1] - fr.tok[c.f], in_frame = c.k * AR_LANES * c.S;
+    c.rows = (int)(n - in_frame < (int64_t)AR_LANES * c.S ? n - in_frame : (int64_t)AR_LANES * c.S);
+    c.base = fr.tok[c.f] + in_frame;
+    return c;
+}
+// (a frame's payload: head [8 bytes], states [K x 64 x u64], word counts [K x u32], words)
+__global__ void __launch_bounds__(AR_LANES) k_attr_rans_encode(const uint16_t* __restrict__ tables, const uint16_t* __restrict__ ctx,
+                                                               const int16_t* __restrict__ tokens, ArFrames fr, uint32_t* __restrict__ scratch,
+                                                               uint8_t* __restrict__ payload, unsigned long long* __restrict__ refused) {
     __shared__ __attribute__((aligned(16))) uint32_t sh[AR_CONTEXTS * AR_ROW];
-    const int f = ar_frame_of(fr, blockIdx.x);
-    ar_load_table(sh, tables + (size_t)f * AR_CONTEXTS * (AR_TOKENS + 1));
-    const int S = fr.steps[f];
-    const int64_t k = (int64_t)blockIdx.x - fr.chunk[f], K = fr.chunk[f + 1] - fr.chunk[f], n = fr.tok[f + 1] - fr.tok[f];
-    const int64_t base = k * AR_LANES * S;
-    const int rows = (int)(n - base < (int64_t)AR_LANES * S ? n - base : (int64_t)AR_LANES * S);
-    uint8_t* mine = payload + fr.pay[f];
-    ar_encode_chunk(sh, ctx + fr.tok[f] + base, tokens + fr.tok[f] + base, rows, scratch + fr.tok[f] + base,
-                    (unsigned long long*)(mine + 8) + k * AR_LANES, (uint32_t*)(mine + 8 + 512 * K) + k, refused + f);
+    const ArChunk c = ar_chunk_of(fr);
+    ar_load_table(sh, tables + (size_t)c.f * AR_CONTEXTS * (AR_TOKENS + 1));
+    uint8_t* mine = payload + fr.pay[c.f];
+    ar_encode_chunk(sh, ctx + c.base, tokens + c.base, c.rows, scratch + c.base, (unsigned long long*)(mine + 8) + c.k * AR_LANES,
+                    (uint32_t*)(mine + 8 + 512 * c.K) + c.k, refused + c.f);
 }
 
-// exclusive scan of the chunks' word counts (one block; thread t owns a run of consecutive chunks) -> offs [K] (saturating: counts a decoder
-// reads are not to be trusted), slot[0] = their sum.  Encoder side: also the payload's head.
-__device__ __forceinline__ void ar_offsets(unsigned long long* part, const uint32_t* __restrict__ wcount, int64_t K, uint32_t* __restrict__ offs,
-                                           long long* __restrict__ slot, uint32_t* __restrict__ head, uint32_t S) {
+// block f: an exclusive scan of the word counts of frame f's chunks (thread t owns a run of consecutive chunks) -> offs [chunk[f] ..) counted
+// from the frame's own first word (saturating: counts a decoder reads are not to be trusted), slot[f] = the frame's words.  Encoder side
+// (with_head): also the payload's head; a frame without chunks has none (its payload is empty).
+__global__ void __launch_bounds__(AR_SCAN_BLOCK) k_attr_rans_offsets(ArFrames fr, uint8_t* payload, uint32_t* __restrict__ offs,
+                                                                     long long* __restrict__ slot, int with_head) {
+    __shared__ unsigned long long part[AR_SCAN_BLOCK];
+    const int f = blockIdx.x;
+    const int64_t K = fr.chunk[f + 1] - fr.chunk[f];
+    if (K <= 0) { if (threadIdx.x == 0) slot[f] = 0; return; }      // (uniform)
+    uint8_t* mine = payload + fr.pay[f];
+    const uint32_t* __restrict__ wcount = (const uint32_t*)(mine + 8 + 512 * K);
+    offs += fr.chunk[f];
     const int64_t per = (K + AR_SCAN_BLOCK - 1) / AR_SCAN_BLOCK;
     const int64_t lo = (int64_t)threadIdx.x * per < K ? (int64_t)threadIdx.x * per : K, hi = lo + per < K ? lo + per : K;
     unsigned long long s = 0;
@@ -179,67 +189,40 @@ __device__ __forceinline__ void ar_offsets(unsigned long long* part, const uint3
     if (threadIdx.x == 0) {
         unsigned long long run = 0;
         for (int i = 0; i < AR_SCAN_BLOCK; ++i) { const unsigned long long v = part[i]; part[i] = run; run += v; }
-        slot[0] = (long long)run;
-        if (head) { head[0] = S; head[1] = (uint32_t)K; }
+        slot[f] = (long long)run;
+        if (with_head) { ((uint32_t*)mine)[0] = (uint32_t)fr.steps[f]; ((uint32_t*)mine)[1] = (uint32_t)K; }
     }
     __syncthreads();
     unsigned long long run = part[threadIdx.x];
     for (int64_t i = lo; i < hi; ++i) { offs[i] = run < 0xffffffffull ? (uint32_t)run : 0xffffffffu; run += wcount[i]; }
 }
-__global__ void __launch_bounds__(AR_SCAN_BLOCK) k_attr_rans_offsets(const uint32_t* __restrict__ wcount, int64_t K, uint32_t* __restrict__ offs,
-                                                                     long long* __restrict__ slot, uint32_t* __restrict__ head, uint32_t S) {
-    __shared__ unsigned long long part[AR_SCAN_BLOCK];
-    ar_offsets(part, wcount, K, offs, slot, head, S);
-}
-// block f: frame f's chunks -> offs [chunk[f] ..) counted from the frame's own first word, slot[f] = the frame's words; a frame without
-// chunks has no head (its payload is empty)
-__global__ void __launch_bounds__(AR_SCAN_BLOCK) k_attr_rans_offsets_batch(ArFrames fr, uint8_t* payload, uint32_t* __restrict__ offs,
-                                                                           long long* __restrict__ slot, int with_head) {
-    __shared__ unsigned long long part[AR_SCAN_BLOCK];
-    const int f = blockIdx.x;
-    const int64_t K = fr.chunk[f + 1] - fr.chunk[f];
-    if (K <= 0) { if (threadIdx.x == 0) slot[f] = 0; return; }      // (uniform)
-    uint8_t* mine = payload + fr.pay[f];
-    ar_offsets(part, (const uint32_t*)(mine + 8 + 512 * K), K, offs + fr.chunk[f], slot + f, with_head ? (uint32_t*)mine : (uint32_t*)nullptr,
-               (uint32_t)fr.steps[f]);
-}
 
-// chunk k's words, from the end of its scratch to their place in the payload
-__global__ void __launch_bounds__(AR_SCAN_BLOCK) k_attr_rans_compact(const uint32_t* __restrict__ scratch, int64_t n, int S, const uint32_t* __restrict__ wcount,
-                                                                     const uint32_t* __restrict__ offs, uint32_t* __restrict__ words) {
-    const int64_t k = blockIdx.x, base = k * AR_LANES * S;
-    const int64_t rows = n - base < (int64_t)AR_LANES * S ? n - base : (int64_t)AR_LANES * S;
-    const uint32_t W = wcount[k];                             // <= rows: the encoder wrote it
-    const uint32_t* __restrict__ src = scratch + base + rows - W;
-    uint32_t* __restrict__ dst = words + offs[k];
-    for (uint32_t i = threadIdx.x; i < W; i += AR_SCAN_BLOCK) dst[i] = src[i];
-}
-__global__ void __launch_bounds__(AR_SCAN_BLOCK) k_attr_rans_compact_batch(const uint32_t* __restrict__ scratch, ArFrames fr, const uint32_t* __restrict__ offs,
-                                                                           uint8_t* __restrict__ payload) {
-    const int f = ar_frame_of(fr, blockIdx.x);
-    const int S = fr.steps[f];
-    const int64_t k = (int64_t)blockIdx.x - fr.chunk[f], K = fr.chunk[f + 1] - fr.chunk[f], n = fr.tok[f + 1] - fr.tok[f];
-    const int64_t base = k * AR_LANES * S;
-    const int64_t rows = n - base < (int64_t)AR_LANES * S ? n - base : (int64_t)AR_LANES * S;
-    const uint32_t* wcount = (const uint32_t*)(payload + fr.pay[f] + 8 + 512 * K);
-    const uint32_t W = wcount[k];                             // <= rows: the encoder wrote it
-    const uint32_t* __restrict__ src = scratch + fr.tok[f] + base + rows - W;
-    uint32_t* __restrict__ dst = (uint32_t*)(wcount + K) + offs[blockIdx.x];
+// a chunk's words, from the end of its scratch to their place in its frame's payload
+__global__ void __launch_bounds__(AR_SCAN_BLOCK) k_attr_rans_compact(const uint32_t* __restrict__ scratch, ArFrames fr, const uint32_t* __restrict__ offs,
+                                                                     uint8_t* __restrict__ payload) {
+    const ArChunk c = ar_chunk_of(fr);
+    const uint32_t* wcount = (const uint32_t*)(payload + fr.pay[c.f] + 8 + 512 * c.K);
+    const uint32_t W = wcount[c.k];                           // <= rows: the encoder wrote it
+    const uint32_t* __restrict__ src = scratch + c.base + c.rows - W;
+    uint32_t* __restrict__ dst = (uint32_t*)(wcount + c.K) + offs[blockIdx.x];
     for (uint32_t i = threadIdx.x; i < W; i += AR_SCAN_BLOCK) dst[i] = src[i];
 }
 
 // ---- decoder ---------------------------------------------------------------------------------------------------------------------------------
-// the context of every token in coding order from the tree's 65 bucket offsets: position p of the order (token 3 p + channel) has split bit
-// d = 63 - b, where b is the last bucket with bucket[b] <= p; ctx = 16 channel + min(d / 3, 15)
-__global__ void __launch_bounds__(AR_SCAN_BLOCK) k_attr_rans_ctx(const int32_t* __restrict__ bucket, int64_t n, uint16_t* __restrict__ ctx /*[n]*/) {
-    __shared__ int32_t sh_b[AR_TOKENS + 1];
-    if (threadIdx.x <= AR_TOKENS) sh_b[threadIdx.x] = bucket[threadIdx.x];
-    __syncthreads();
-    const int64_t p = (int64_t)blockIdx.x * AR_SCAN_BLOCK + threadIdx.x;
+// the context of every token in coding order from the trees' bucket offsets: position p of the coding order (token 3 p + channel) lies in
+// the last frame f with tok[f] <= 3 p, at position q = p - tok[f] / 3 of that frame's own order, whose 65 offsets are row f of bucket
+// [frames, 65]; its split bit is d = 63 - b, where b is the last bucket with row[b] <= q; ctx = 16 channel + min(d / 3, 15).  tok[] of the
+// frames of a batch are multiples of 3; the last position of a single frame may hold fewer than three tokens, so the tail stores are guarded.
+__global__ void __launch_bounds__(AR_SCAN_BLOCK) k_attr_rans_ctx(const int32_t* __restrict__ bucket, ArFrames fr, uint16_t* __restrict__ ctx) {
+    const int64_t p = (int64_t)blockIdx.x * AR_SCAN_BLOCK + threadIdx.x, n = fr.tok[fr.frames];
     if (3 * p >= n) return;
+    int f = 0;
+    for (int b = 1; b < AR_MAX_FRAMES; ++b) f += (b < fr.frames && fr.tok[b] <= 3 * p) ? 1 : 0;
+    const int32_t* __restrict__ row = bucket + f * (AR_TOKENS + 1);
+    const int64_t q = p - fr.tok[f] / 3;
     int b = 0;
 #pragma unroll
-    for (int step = 32; step > 0; step >>= 1) b += (b + step <= 63 && (int64_t)sh_b[b + step] <= p) ? step : 0;        // b stays in 0 .. 63
+    for (int step = 32; step > 0; step >>= 1) b += (b + step <= 63 && (int64_t)row[b + step] <= q) ? step : 0;         // b stays in 0 .. 63
     const int d = 63 - b;
     const uint16_t level = (uint16_t)(d / 3 < 15 ? d / 3 : 15);
     ctx[3 * p] = level;
@@ -341,160 +324,53 @@ __device__ __forceinline__ void ar_decode_chunk(const uint32_t* sh, uint32_t* ri
         if (any_bad) atomicAdd(result + 1, 1ull);
     }
 }
-__global__ void __launch_bounds__(AR_LANES) k_attr_rans_decode(const uint16_t* __restrict__ table, const uint16_t* __restrict__ ctx, int64_t n, int S,
-                                                               const unsigned long long* __restrict__ states, const uint32_t* __restrict__ wcount,
-                                                               const uint32_t* __restrict__ offs, const uint32_t* __restrict__ words,
-                                                               int64_t words_total, int16_t* __restrict__ tokens,
-                                                               unsigned long long* __restrict__ result /*[0] tokens that are 63, [1] unsound chunks*/) {
-    __shared__ __attribute__((aligned(16))) uint32_t sh[AR_CONTEXTS * AR_ROW];
-    __shared__ uint32_t ring[AR_RING];
-    ar_load_table(sh, table);
-    const int64_t k = blockIdx.x, base = k * AR_LANES * S;
-    const int rows = (int)(n - base < (int64_t)AR_LANES * S ? n - base : (int64_t)AR_LANES * S);
-    ar_decode_chunk(sh, ring, ctx + base, rows, states + k * AR_LANES, wcount[k], (int64_t)offs[k], words, words_total, tokens + base, result);
-}
-
-// the contexts of a batch: position p of the batch's coding order lies in the last frame f with tok[f] <= 3 p, at position p - tok[f] / 3 of
-// that frame's own order, whose 65 offsets are row f of bucket [frames, 65]
-__global__ void __launch_bounds__(AR_SCAN_BLOCK) k_attr_rans_ctx_batch(const int32_t* __restrict__ bucket, ArFrames fr, uint16_t* __restrict__ ctx) {
-    const int64_t p = (int64_t)blockIdx.x * AR_SCAN_BLOCK + threadIdx.x;
-    if (3 * p >= fr.tok[fr.frames]) return;
-    int f = 0;
-    for (int b = 1; b < AR_MAX_FRAMES; ++b) f += (b < fr.frames && fr.tok[b] <= 3 * p) ? 1 : 0;
-    const int32_t* __restrict__ row = bucket + f * (AR_TOKENS + 1);
-    const int64_t q = p - fr.tok[f] / 3;
-    int b = 0;
-#pragma unroll
-    for (int step = 32; step > 0; step >>= 1) b += (b + step <= 63 && (int64_t)row[b + step] <= q) ? step : 0;         // b stays in 0 .. 63
-    const int d = 63 - b;
-    const uint16_t level = (uint16_t)(d / 3 < 15 ? d / 3 : 15);
-    ctx[3 * p] = level; ctx[3 * p + 1] = (uint16_t)(16 + level); ctx[3 * p + 2] = (uint16_t)(32 + level);          // (tok[] are multiples of 3)
-}
 // result [2 f], [2 f + 1]: frame f's tokens that are 63 and its unsound chunks
-__global__ void __launch_bounds__(AR_LANES) k_attr_rans_decode_batch(const uint16_t* __restrict__ tables, const uint16_t* __restrict__ ctx, ArFrames fr,
-                                                                     const uint8_t* __restrict__ payload, const uint32_t* __restrict__ offs,
-                                                                     int16_t* __restrict__ tokens, unsigned long long* __restrict__ result) {
+__global__ void __launch_bounds__(AR_LANES) k_attr_rans_decode(const uint16_t* __restrict__ tables, const uint16_t* __restrict__ ctx, ArFrames fr,
+                                                               const uint8_t* __restrict__ payload, const uint32_t* __restrict__ offs,
+                                                               int16_t* __restrict__ tokens, unsigned long long* __restrict__ result) {
     __shared__ __attribute__((aligned(16))) uint32_t sh[AR_CONTEXTS * AR_ROW];
     __shared__ uint32_t ring[AR_RING];
-    const int f = ar_frame_of(fr, blockIdx.x);
-    ar_load_table(sh, tables + (size_t)f * AR_CONTEXTS * (AR_TOKENS + 1));
-    const int S = fr.steps[f];
-    const int64_t k = (int64_t)blockIdx.x - fr.chunk[f], K = fr.chunk[f + 1] - fr.chunk[f], n = fr.tok[f + 1] - fr.tok[f];
-    const int64_t base = k * AR_LANES * S;
-    const int rows = (int)(n - base < (int64_t)AR_LANES * S ? n - base : (int64_t)AR_LANES * S);
-    const uint8_t* mine = payload + fr.pay[f];
-    const uint32_t* wcount = (const uint32_t*)(mine + 8 + 512 * K);
-    ar_decode_chunk(sh, ring, ctx + fr.tok[f] + base, rows, (const unsigned long long*)(mine + 8) + k * AR_LANES, wcount[k],
-                    (int64_t)offs[blockIdx.x], wcount + K, fr.words[f], tokens + fr.tok[f] + base, result + 2 * f);
+    const ArChunk c = ar_chunk_of(fr);
+    ar_load_table(sh, tables + (size_t)c.f * AR_CONTEXTS * (AR_TOKENS + 1));
+    const uint8_t* mine = payload + fr.pay[c.f];
+    const uint32_t* wcount = (const uint32_t*)(mine + 8 + 512 * c.K);
+    ar_decode_chunk(sh, ring, ctx + c.base, c.rows, (const unsigned long long*)(mine + 8) + c.k * AR_LANES, wcount[c.k], (int64_t)offs[blockIdx.x],
+                    wcount + c.K, fr.words[c.f], tokens + c.base, result + 2 * c.f);
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------------------
-// workspace: [slot: 4 x int64][offs: K x u32, padded to 8 bytes][encoder: scratch, n x u32 | decoder: contexts, n x u16]
-static size_t ar_offs_bytes(int64_t K) { return (size_t)((K * 4 + 7) / 8 * 8); }
-
-extern "C" int64_t pcgc_attr_rans_workspace_bytes(int64_t n, int steps) {
-    if (n < 0) n = 0;
-    if (steps < 1) steps = 1;
-    return 32 + (int64_t)ar_offs_bytes(ar_chunks(n, steps)) + n * 4 + 64;
-}
-
-static long long* ar_host_slot() {
-    static thread_local long long* host = nullptr;
-    if (!host && hipHostMalloc((void**)&host, 64, hipHostMallocDefault) != hipSuccess) host = nullptr;
-    return host;
-}
-
-extern "C" int pcgc_attr_rans_encode(const uint16_t* table, const uint16_t* ctx, const int16_t* tokens, int64_t n, int steps, uint8_t* payload,
-                                     size_t payload_capacity, int64_t* host2, void* workspace, size_t workspace_bytes, void* stream) {
-    PCGC_REQUIRE(n >= 1 && n < ((int64_t)1 << 31), "bad token count");
-    PCGC_REQUIRE(steps >= 1 && steps <= AR_MAX_STEPS, "steps per chunk outside 1 .. 2^24");
-    PCGC_REQUIRE(table && ctx && tokens && payload && host2, "null argument");
-    const int64_t K = ar_chunks(n, steps);
-    PCGC_REQUIRE(payload_capacity >= (size_t)(8 + 516 * K + 4 * n) && ((uintptr_t)payload & 7) == 0, "payload buffer too small or misaligned");
-    PCGC_REQUIRE(workspace && workspace_bytes >= (size_t)pcgc_attr_rans_workspace_bytes(n, steps) && ((uintptr_t)workspace & 7) == 0, "workspace too small or misaligned");
-    long long* slot = (long long*)workspace;
-    uint32_t* offs = (uint32_t*)((char*)workspace + 32);
-    uint32_t* scratch = (uint32_t*)((char*)workspace + 32 + ar_offs_bytes(K));
-    unsigned long long* states = (unsigned long long*)(payload + 8);
-    uint32_t* wcount = (uint32_t*)(payload + 8 + 512 * K);
-    uint32_t* words = wcount + K;
-    long long* host = ar_host_slot();
-    if (!host) { pcgc_set_error("attr_rans_encode: cannot allocate pinned memory"); return -1; }
-    hipError_t e = hipMemsetAsync(slot, 0, 32, S(stream));
-    if (e != hipSuccess) { pcgc_set_error("attr_rans_encode: %s", hipGetErrorString(e)); return -1; }
-    hipLaunchKernelGGL(k_attr_rans_encode, dim3((unsigned)K), dim3(AR_LANES), 0, S(stream), table, ctx, tokens, n, steps, scratch, states, wcount,
-                       (unsigned long long*)(slot + 1));
-    PCGC_CHECK_LAUNCH("attr_rans_encode");
-    hipLaunchKernelGGL(k_attr_rans_offsets, dim3(1), dim3(AR_SCAN_BLOCK), 0, S(stream), (const uint32_t*)wcount, K, offs, slot, (uint32_t*)payload, (uint32_t)steps);
-    PCGC_CHECK_LAUNCH("attr_rans_encode");
-    hipLaunchKernelGGL(k_attr_rans_compact, dim3((unsigned)K), dim3(AR_SCAN_BLOCK), 0, S(stream), (const uint32_t*)scratch, n, steps, (const uint32_t*)wcount,
-                       (const uint32_t*)offs, words);
-    PCGC_CHECK_LAUNCH("attr_rans_encode");
-    e = hipMemcpyAsync(host, slot, 2 * sizeof(long long), hipMemcpyDeviceToHost, S(stream));
-    if (e == hipSuccess) e = hipStreamSynchronize(S(stream));
-    if (e != hipSuccess) { pcgc_set_error("attr_rans_encode: %s", hipGetErrorString(e)); return -1; }
-    host2[0] = 8 + 516 * K + 4 * (int64_t)host[0];
-    host2[1] = (int64_t)host[1];
-    return 0;
-}
-
-extern "C" int pcgc_attr_rans_decode(const uint16_t* table, const int32_t* bucket, int64_t n, const uint8_t* payload, int64_t payload_bytes, int steps,
-                                     int16_t* tokens, int64_t* host2, void* workspace, size_t workspace_bytes, void* stream) {
-    PCGC_REQUIRE(n >= 1 && n < ((int64_t)1 << 31), "bad token count");
-    PCGC_REQUIRE(table && bucket && tokens && payload && host2, "null argument");
-    PCGC_REQUIRE(((uintptr_t)payload & 7) == 0, "payload misaligned");
-    PCGC_REQUIRE(steps >= 1 && steps <= AR_MAX_STEPS, "steps per chunk outside 1 .. 2^24");
-    long long* host = ar_host_slot();
-    if (!host) { pcgc_set_error("attr_rans_decode: cannot allocate pinned memory"); return -1; }
-    const int64_t K = ar_chunks(n, steps);            // (the head's own S and K are the caller's to compare: ops.attr_rans_decode)
-    PCGC_REQUIRE(payload_bytes >= 8 + 516 * K && (payload_bytes - 8 - 516 * K) % 4 == 0, "payload cut inside its tables or not whole words");
-    const int64_t words_total = (payload_bytes - 8 - 516 * K) / 4;
-    PCGC_REQUIRE(workspace && workspace_bytes >= (size_t)pcgc_attr_rans_workspace_bytes(n, steps) && ((uintptr_t)workspace & 7) == 0, "workspace too small or misaligned");
-    long long* slot = (long long*)workspace;
-    uint32_t* offs = (uint32_t*)((char*)workspace + 32);
-    uint16_t* ctx = (uint16_t*)((char*)workspace + 32 + ar_offs_bytes(K));
-    const unsigned long long* states = (const unsigned long long*)(payload + 8);
-    const uint32_t* wcount = (const uint32_t*)(payload + 8 + 512 * K);
-    const uint32_t* words = wcount + K;
-    hipError_t e = hipMemsetAsync(slot, 0, 32, S(stream));
-    if (e != hipSuccess) { pcgc_set_error("attr_rans_decode: %s", hipGetErrorString(e)); return -1; }
-    hipLaunchKernelGGL(k_attr_rans_ctx, dim3(grid_for((n + 2) / 3, AR_SCAN_BLOCK)), dim3(AR_SCAN_BLOCK), 0, S(stream), bucket, n, ctx);
-    PCGC_CHECK_LAUNCH("attr_rans_decode");
-    hipLaunchKernelGGL(k_attr_rans_offsets, dim3(1), dim3(AR_SCAN_BLOCK), 0, S(stream), wcount, K, offs, slot, (uint32_t*)nullptr, 0u);
-    PCGC_CHECK_LAUNCH("attr_rans_decode");
-    hipLaunchKernelGGL(k_attr_rans_decode, dim3((unsigned)K), dim3(AR_LANES), 0, S(stream), table, (const uint16_t*)ctx, n, steps, states, wcount,
-                       (const uint32_t*)offs, words, words_total, tokens, (unsigned long long*)(slot + 1));
-    PCGC_CHECK_LAUNCH("attr_rans_decode");
-    e = hipMemcpyAsync(host, slot, 3 * sizeof(long long), hipMemcpyDeviceToHost, S(stream));
-    if (e == hipSuccess) e = hipStreamSynchronize(S(stream));
-    if (e != hipSuccess) { pcgc_set_error("attr_rans_decode: %s", hipGetErrorString(e)); return -1; }
-    host2[0] = (int64_t)host[1];
-    host2[1] = (int64_t)host[2] + (host[0] != words_total ? 1 : 0);      // unsound chunks (+ 1: the word counts do not add up to the payload)
-    return 0;
-}
-
-// ---- a batch of frames ------------------------------------------------------------------------------------------------------------------------
+// The batch entries and the single ones run the same two bodies below over an ArFrames; a single entry builds the ArFrames of one frame and
+// translates the body's per-frame answers into its documented host2.
 // workspace: [slot: 64 x int64 = words per frame [16], then the encoder's refused tokens per frame [16] or the decoder's result [32]]
 //            [offs: K x u32, padded to 8 bytes][encoder: scratch, n x u32 | decoder: contexts, n x u16]
+constexpr size_t AR_SLOT_BYTES = 4 * AR_MAX_FRAMES * sizeof(long long);
+static size_t ar_offs_bytes(int64_t K) { return (size_t)((K * 4 + 7) / 8 * 8); }
+
 extern "C" int64_t pcgc_attr_rans_batch_workspace_bytes(int64_t n, int64_t chunks) {
     if (n < 0) n = 0;
     if (chunks < 0) chunks = 0;
-    return 512 + (int64_t)ar_offs_bytes(chunks) + n * 4 + 64;
+    return (int64_t)AR_SLOT_BYTES + (int64_t)ar_offs_bytes(chunks) + n * 4 + 64;
 }
-static long long* ar_host_slot_batch() {
-    static thread_local long long* host = nullptr;
-    if (!host && hipHostMalloc((void**)&host, 512, hipHostMallocDefault) != hipSuccess) host = nullptr;
-    return host;
+extern "C" int64_t pcgc_attr_rans_workspace_bytes(int64_t n, int steps) {
+    if (n < 0) n = 0;
+    if (steps < 1) steps = 1;
+    return pcgc_attr_rans_batch_workspace_bytes(n, ar_chunks(n, steps));
 }
-// fills fr from the host arrays; false when they are not a batch: tok ascending multiples of 3 from 0, steps in range, K_f chunks each
-static bool ar_frames_of(int frames, const int64_t* tok, const int32_t* steps, const int64_t* pay, ArFrames& fr, bool all) {
+
+#define AR_REQUIRE(who, cond, msg) do { if (!(cond)) { pcgc_set_error("%s: %s", who, msg); return -2; } } while (0)
+#define AR_CHECK_HIP(who, e) do { if ((e) != hipSuccess) { pcgc_set_error("%s: %s", (who) + 5, hipGetErrorString(e)); return -1; } } while (0)
+
+// fills fr from the host arrays; false when they are not a batch: tok ascending from 0 (thirds, the batch entries' own demand: in multiples
+// of 3), steps in range, K_f chunks each
+static bool ar_frames_of(int frames, const int64_t* tok, const int32_t* steps, const int64_t* pay, ArFrames& fr, bool all, bool thirds) {
     memset(&fr, 0, sizeof(fr));
     if (frames < 1 || frames > AR_MAX_FRAMES || !tok || !steps || !pay || tok[0] != 0) return false;
     fr.frames = frames;
     int64_t K = 0;
     for (int f = 0; f < frames; ++f) {
         const int64_t n = tok[f + 1] - tok[f];
-        if (n < 0 || n % 3 || tok[f + 1] >= ((int64_t)1 << 31) || steps[f] < 0 || steps[f] > AR_MAX_STEPS || (pay[f] & 7) || pay[f] < 0) return false;
+        if (n < 0 || (thirds && n % 3) || tok[f + 1] >= ((int64_t)1 << 31) || steps[f] < 0 || steps[f] > AR_MAX_STEPS || (pay[f] & 7) || pay[f] < 0)
+            return false;
         if (all && n > 0 && steps[f] < 1) return false;
         fr.tok[f] = tok[f]; fr.pay[f] = pay[f]; fr.steps[f] = steps[f]; fr.chunk[f] = (int)K;
         K += (n > 0 && steps[f] > 0) ? ar_chunks(n, steps[f]) : 0;
@@ -503,36 +379,57 @@ static bool ar_frames_of(int frames, const int64_t* tok, const int32_t* steps, c
     for (int f = frames; f <= AR_MAX_FRAMES; ++f) { fr.tok[f] = tok[frames]; fr.chunk[f] = (int)K; }
     return true;
 }
+static bool ar_frame_of_one(int64_t n, int steps, ArFrames& fr) {
+    const int64_t tok[2] = {0, n}, pay = 0;
+    const int32_t s = steps;
+    return ar_frames_of(1, tok, &s, &pay, fr, true, false);
+}
 
-extern "C" int pcgc_attr_rans_encode_batch(const uint16_t* tables, const uint16_t* ctx, const int16_t* tokens, int frames, const int64_t* tok,
-                                           const int32_t* steps, uint8_t* payload, const int64_t* pay, int64_t* host, void* workspace,
-                                           size_t workspace_bytes, void* stream) {
-    ArFrames fr;
-    PCGC_REQUIRE(ar_frames_of(frames, tok, steps, pay, fr, true), "1 to 16 frames; token offsets ascending multiples of 3 below 2^31; steps per chunk 1 .. 2^24; payload offsets multiples of 8");
-    PCGC_REQUIRE(tables && ctx && tokens && payload && host && ((uintptr_t)payload & 7) == 0, "null or misaligned argument");
-    const int64_t n = fr.tok[frames], K = fr.chunk[frames];
-    PCGC_REQUIRE(n >= 1, "no token: nothing to launch");
-    for (int f = 0; f < frames; ++f)
-        PCGC_REQUIRE(pay[f + 1] - pay[f] >= (fr.chunk[f + 1] > fr.chunk[f] ? 8 + 516 * (int64_t)(fr.chunk[f + 1] - fr.chunk[f]) + 4 * (tok[f + 1] - tok[f]) : 0),
-                     "payload room of a frame below 8 + 516 K + 4 n bytes");
-    PCGC_REQUIRE(workspace && workspace_bytes >= (size_t)pcgc_attr_rans_batch_workspace_bytes(n, K) && ((uintptr_t)workspace & 7) == 0, "workspace too small or misaligned");
-    long long* slot = (long long*)workspace;
-    uint32_t* offs = (uint32_t*)((char*)workspace + 512);
-    uint32_t* scratch = (uint32_t*)((char*)workspace + 512 + ar_offs_bytes(K));
-    long long* hostslot = ar_host_slot_batch();
-    if (!hostslot) { pcgc_set_error("attr_rans_encode_batch: cannot allocate pinned memory"); return -1; }
-    hipError_t e = hipMemsetAsync(slot, 0, 512, S(stream));
-    if (e != hipSuccess) { pcgc_set_error("attr_rans_encode_batch: %s", hipGetErrorString(e)); return -1; }
-    hipLaunchKernelGGL(k_attr_rans_encode_batch, dim3((unsigned)K), dim3(AR_LANES), 0, S(stream), tables, ctx, tokens, fr, scratch, payload,
+static long long* ar_host_slot() {
+    static thread_local long long* host = nullptr;
+    if (!host && hipHostMalloc((void**)&host, AR_SLOT_BYTES, hipHostMallocDefault) != hipSuccess) host = nullptr;
+    return host;
+}
+// both bodies: the workspace is checked and carved and its slots are zeroed; rest: the encoder's scratch or the decoder's contexts
+static int ar_begin(const char* who, const ArFrames& fr, void* workspace, size_t workspace_bytes, long long*& host, long long*& slot, uint32_t*& offs,
+                    void*& rest, hipStream_t s) {
+    const int64_t n = fr.tok[fr.frames], K = fr.chunk[fr.frames];
+    AR_REQUIRE(who, workspace && workspace_bytes >= (size_t)pcgc_attr_rans_batch_workspace_bytes(n, K) && ((uintptr_t)workspace & 7) == 0,
+               "workspace too small or misaligned");
+    slot = (long long*)workspace;
+    offs = (uint32_t*)((char*)workspace + AR_SLOT_BYTES);
+    rest = (char*)workspace + AR_SLOT_BYTES + ar_offs_bytes(K);
+    host = ar_host_slot();
+    if (!host) { pcgc_set_error("%s: cannot allocate pinned memory", who + 5); return -1; }
+    hipError_t e = hipMemsetAsync(slot, 0, AR_SLOT_BYTES, s);
+    AR_CHECK_HIP(who, e);
+    return 0;
+}
+// the first `count` slots brought down, the stream synchronised
+static int ar_end(const char* who, long long* host, const long long* slot, int count, hipStream_t s) {
+    hipError_t e = hipMemcpyAsync(host, slot, count * sizeof(long long), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    AR_CHECK_HIP(who, e);
+    return 0;
+}
+
+// host [2 frames] = every frame's payload bytes (8 + 516 K_f + 4 words; 0 for a frame without chunks), then its refused tokens
+static int ar_encode(const char* who, const uint16_t* tables, const uint16_t* ctx, const int16_t* tokens, const ArFrames& fr, uint8_t* payload,
+                     int64_t* host, void* workspace, size_t workspace_bytes, hipStream_t s) {
+    long long *hostslot, *slot;
+    uint32_t* offs;
+    void* scratch;
+    if (int r = ar_begin(who, fr, workspace, workspace_bytes, hostslot, slot, offs, scratch, s)) return r;
+    const int frames = fr.frames;
+    const unsigned K = (unsigned)fr.chunk[frames];
+    hipLaunchKernelGGL(k_attr_rans_encode, dim3(K), dim3(AR_LANES), 0, s, tables, ctx, tokens, fr, (uint32_t*)scratch, payload,
                        (unsigned long long*)(slot + AR_MAX_FRAMES));
-    PCGC_CHECK_LAUNCH("attr_rans_encode_batch");
-    hipLaunchKernelGGL(k_attr_rans_offsets_batch, dim3((unsigned)frames), dim3(AR_SCAN_BLOCK), 0, S(stream), fr, payload, offs, slot, 1);
-    PCGC_CHECK_LAUNCH("attr_rans_encode_batch");
-    hipLaunchKernelGGL(k_attr_rans_compact_batch, dim3((unsigned)K), dim3(AR_SCAN_BLOCK), 0, S(stream), (const uint32_t*)scratch, fr, (const uint32_t*)offs, payload);
-    PCGC_CHECK_LAUNCH("attr_rans_encode_batch");
-    e = hipMemcpyAsync(hostslot, slot, 2 * AR_MAX_FRAMES * sizeof(long long), hipMemcpyDeviceToHost, S(stream));
-    if (e == hipSuccess) e = hipStreamSynchronize(S(stream));
-    if (e != hipSuccess) { pcgc_set_error("attr_rans_encode_batch: %s", hipGetErrorString(e)); return -1; }
+    PCGC_CHECK_LAUNCH(who + 5);
+    hipLaunchKernelGGL(k_attr_rans_offsets, dim3((unsigned)frames), dim3(AR_SCAN_BLOCK), 0, s, fr, payload, offs, slot, 1);
+    PCGC_CHECK_LAUNCH(who + 5);
+    hipLaunchKernelGGL(k_attr_rans_compact, dim3(K), dim3(AR_SCAN_BLOCK), 0, s, (const uint32_t*)scratch, fr, (const uint32_t*)offs, payload);
+    PCGC_CHECK_LAUNCH(who + 5);
+    if (int r = ar_end(who, hostslot, slot, 2 * AR_MAX_FRAMES, s)) return r;
     for (int f = 0; f < frames; ++f) {
         const int64_t Kf = fr.chunk[f + 1] - fr.chunk[f];
         host[f] = Kf ? 8 + 516 * Kf + 4 * (int64_t)hostslot[f] : 0;
@@ -540,39 +437,24 @@ extern "C" int pcgc_attr_rans_encode_batch(const uint16_t* tables, const uint16_
     }
     return 0;
 }
-
-extern "C" int pcgc_attr_rans_decode_batch(const uint16_t* tables, const int32_t* bucket, int frames, const int64_t* tok, const int32_t* steps,
-                                           const uint8_t* payload, const int64_t* pay, const int64_t* pay_bytes, int16_t* tokens, int64_t* host,
-                                           void* workspace, size_t workspace_bytes, void* stream) {
-    ArFrames fr;
-    PCGC_REQUIRE(ar_frames_of(frames, tok, steps, pay, fr, false), "1 to 16 frames; token offsets ascending multiples of 3 below 2^31; steps per chunk 0 .. 2^24; payload offsets multiples of 8");
-    PCGC_REQUIRE(tables && bucket && tokens && payload && pay_bytes && host && ((uintptr_t)payload & 7) == 0, "null or misaligned argument");
-    const int64_t n = fr.tok[frames], K = fr.chunk[frames];
-    PCGC_REQUIRE(n >= 1 && K >= 1, "no chunk: nothing to launch");
-    for (int f = 0; f < frames; ++f) {
-        const int64_t Kf = fr.chunk[f + 1] - fr.chunk[f];
-        if (!Kf) continue;
-        PCGC_REQUIRE(pay_bytes[f] >= 8 + 516 * Kf && (pay_bytes[f] - 8 - 516 * Kf) % 4 == 0, "a payload cut inside its tables or not whole words");
-        fr.words[f] = (pay_bytes[f] - 8 - 516 * Kf) / 4;
-    }
-    PCGC_REQUIRE(workspace && workspace_bytes >= (size_t)pcgc_attr_rans_batch_workspace_bytes(n, K) && ((uintptr_t)workspace & 7) == 0, "workspace too small or misaligned");
-    long long* slot = (long long*)workspace;
-    uint32_t* offs = (uint32_t*)((char*)workspace + 512);
-    uint16_t* ctx = (uint16_t*)((char*)workspace + 512 + ar_offs_bytes(K));
-    long long* hostslot = ar_host_slot_batch();
-    if (!hostslot) { pcgc_set_error("attr_rans_decode_batch: cannot allocate pinned memory"); return -1; }
-    hipError_t e = hipMemsetAsync(slot, 0, 512, S(stream));
-    if (e != hipSuccess) { pcgc_set_error("attr_rans_decode_batch: %s", hipGetErrorString(e)); return -1; }
-    hipLaunchKernelGGL(k_attr_rans_ctx_batch, dim3(grid_for(n / 3, AR_SCAN_BLOCK)), dim3(AR_SCAN_BLOCK), 0, S(stream), bucket, fr, ctx);
-    PCGC_CHECK_LAUNCH("attr_rans_decode_batch");
-    hipLaunchKernelGGL(k_attr_rans_offsets_batch, dim3((unsigned)frames), dim3(AR_SCAN_BLOCK), 0, S(stream), fr, const_cast<uint8_t*>(payload), offs, slot, 0);
-    PCGC_CHECK_LAUNCH("attr_rans_decode_batch");
-    hipLaunchKernelGGL(k_attr_rans_decode_batch, dim3((unsigned)K), dim3(AR_LANES), 0, S(stream), tables, (const uint16_t*)ctx, fr, payload,
+// fr.words[f]: the words of frame f's payload behind its tables.  host [2 frames] = every frame's tokens that are 63, then its unsound chunks
+// (+ 1: the word counts do not add up to the payload); 0 and 0 for a frame without chunks
+static int ar_decode(const char* who, const uint16_t* tables, const int32_t* bucket, const ArFrames& fr, const uint8_t* payload, int16_t* tokens,
+                     int64_t* host, void* workspace, size_t workspace_bytes, hipStream_t s) {
+    long long *hostslot, *slot;
+    uint32_t* offs;
+    void* ctx;
+    if (int r = ar_begin(who, fr, workspace, workspace_bytes, hostslot, slot, offs, ctx, s)) return r;
+    const int frames = fr.frames;
+    const int64_t n = fr.tok[frames];
+    hipLaunchKernelGGL(k_attr_rans_ctx, dim3(grid_for((n + 2) / 3, AR_SCAN_BLOCK)), dim3(AR_SCAN_BLOCK), 0, s, bucket, fr, (uint16_t*)ctx);
+    PCGC_CHECK_LAUNCH(who + 5);
+    hipLaunchKernelGGL(k_attr_rans_offsets, dim3((unsigned)frames), dim3(AR_SCAN_BLOCK), 0, s, fr, const_cast<uint8_t*>(payload), offs, slot, 0);
+    PCGC_CHECK_LAUNCH(who + 5);
+    hipLaunchKernelGGL(k_attr_rans_decode, dim3((unsigned)fr.chunk[frames]), dim3(AR_LANES), 0, s, tables, (const uint16_t*)ctx, fr, payload,
                        (const uint32_t*)offs, tokens, (unsigned long long*)(slot + AR_MAX_FRAMES));
-    PCGC_CHECK_LAUNCH("attr_rans_decode_batch");
-    e = hipMemcpyAsync(hostslot, slot, 3 * AR_MAX_FRAMES * sizeof(long long), hipMemcpyDeviceToHost, S(stream));
-    if (e == hipSuccess) e = hipStreamSynchronize(S(stream));
-    if (e != hipSuccess) { pcgc_set_error("attr_rans_decode_batch: %s", hipGetErrorString(e)); return -1; }
+    PCGC_CHECK_LAUNCH(who + 5);
+    if (int r = ar_end(who, hostslot, slot, 3 * AR_MAX_FRAMES, s)) return r;
     for (int f = 0; f < frames; ++f) {
         const bool here = fr.chunk[f + 1] > fr.chunk[f];
         host[f] = here ? (int64_t)hostslot[AR_MAX_FRAMES + 2 * f] : 0;
@@ -580,3 +462,61 @@ extern "C" int pcgc_attr_rans_decode_batch(const uint16_t* tables, const int32_t
     }
     return 0;
 }
+
+// ---- one frame: any n; host2 = {payload bytes, refused tokens} and {tokens that are 63, unsound chunks} are the body's answers for frame 0
+extern "C" int pcgc_attr_rans_encode(const uint16_t* table, const uint16_t* ctx, const int16_t* tokens, int64_t n, int steps, uint8_t* payload,
+                                     size_t payload_capacity, int64_t* host2, void* workspace, size_t workspace_bytes, void* stream) {
+    PCGC_REQUIRE(n >= 1 && n < ((int64_t)1 << 31), "bad token count");
+    PCGC_REQUIRE(steps >= 1 && steps <= AR_MAX_STEPS, "steps per chunk outside 1 .. 2^24");
+    PCGC_REQUIRE(table && ctx && tokens && payload && host2, "null argument");
+    ArFrames fr;
+    PCGC_REQUIRE(ar_frame_of_one(n, steps, fr), "bad token count");
+    PCGC_REQUIRE(payload_capacity >= (size_t)(8 + 516 * (int64_t)fr.chunk[1] + 4 * n) && ((uintptr_t)payload & 7) == 0,
+                 "payload buffer too small or misaligned");
+    return ar_encode(__func__, table, ctx, tokens, fr, payload, host2, workspace, workspace_bytes, S(stream));
+}
+
+extern "C" int pcgc_attr_rans_decode(const uint16_t* table, const int32_t* bucket, int64_t n, const uint8_t* payload, int64_t payload_bytes, int steps,
+                                     int16_t* tokens, int64_t* host2, void* workspace, size_t workspace_bytes, void* stream) {
+    PCGC_REQUIRE(n >= 1 && n < ((int64_t)1 << 31), "bad token count");
+    PCGC_REQUIRE(table && bucket && tokens && payload && host2, "null argument");
+    PCGC_REQUIRE(((uintptr_t)payload & 7) == 0, "payload misaligned");
+    PCGC_REQUIRE(steps >= 1 && steps <= AR_MAX_STEPS, "steps per chunk outside 1 .. 2^24");
+    ArFrames fr;
+    PCGC_REQUIRE(ar_frame_of_one(n, steps, fr), "bad token count");
+    const int64_t K = fr.chunk[1];                    // (the head's own S and K are the caller's to compare: ops.attr_rans_decode)
+    PCGC_REQUIRE(payload_bytes >= 8 + 516 * K && (payload_bytes - 8 - 516 * K) % 4 == 0, "payload cut inside its tables or not whole words");
+    fr.words[0] = (payload_bytes - 8 - 516 * K) / 4;
+    return ar_decode(__func__, table, bucket, fr, payload, tokens, host2, workspace, workspace_bytes, S(stream));
+}
+
+// ---- a batch of frames: per-frame token counts in multiples of 3
+extern "C" int pcgc_attr_rans_encode_batch(const uint16_t* tables, const uint16_t* ctx, const int16_t* tokens, int frames, const int64_t* tok,
+                                           const int32_t* steps, uint8_t* payload, const int64_t* pay, int64_t* host, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    ArFrames fr;
+    PCGC_REQUIRE(ar_frames_of(frames, tok, steps, pay, fr, true, true), "1 to 16 frames; token offsets ascending multiples of 3 below 2^31; steps per chunk 1 .. 2^24; payload offsets multiples of 8");
+    PCGC_REQUIRE(tables && ctx && tokens && payload && host && ((uintptr_t)payload & 7) == 0, "null or misaligned argument");
+    PCGC_REQUIRE(fr.tok[frames] >= 1, "no token: nothing to launch");
+    for (int f = 0; f < frames; ++f)
+        PCGC_REQUIRE(pay[f + 1] - pay[f] >= (fr.chunk[f + 1] > fr.chunk[f] ? 8 + 516 * (int64_t)(fr.chunk[f + 1] - fr.chunk[f]) + 4 * (tok[f + 1] - tok[f]) : 0),
+                     "payload room of a frame below 8 + 516 K + 4 n bytes");
+    return ar_encode(__func__, tables, ctx, tokens, fr, payload, host, workspace, workspace_bytes, S(stream));
+}
+
+extern "C" int pcgc_attr_rans_decode_batch(const uint16_t* tables, const int32_t* bucket, int frames, const int64_t* tok, const int32_t* steps,
+                                           const uint8_t* payload, const int64_t* pay, const int64_t* pay_bytes, int16_t* tokens, int64_t* host,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+    ArFrames fr;
+    PCGC_REQUIRE(ar_frames_of(frames, tok, steps, pay, fr, false, true), "1 to 16 frames; token offsets ascending multiples of 3 below 2^31; steps per chunk 0 .. 2^24; payload offsets multiples of 8");
+    PCGC_REQUIRE(tables && bucket && tokens && payload && pay_bytes && host && ((uintptr_t)payload & 7) == 0, "null or misaligned argument");
+    PCGC_REQUIRE(fr.tok[frames] >= 1 && fr.chunk[frames] >= 1, "no chunk: nothing to launch");
+    for (int f = 0; f < frames; ++f) {
+        const int64_t Kf = fr.chunk[f + 1] - fr.chunk[f];
+        if (!Kf) continue;
+        PCGC_REQUIRE(pay_bytes[f] >= 8 + 516 * Kf && (pay_bytes[f] - 8 - 516 * Kf) % 4 == 0, "a payload cut inside its tables or not whole words");
+        fr.words[f] = (pay_bytes[f] - 8 - 516 * Kf) / 4;
+    }
+    return ar_decode(__func__, tables, bucket, fr, payload, tokens, host, workspace, workspace_bytes, S(stream));
+}
+

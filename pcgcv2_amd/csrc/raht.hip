@@ -5,9 +5,10 @@
 //                         the number of adjacent equal keys, and whether a row lies outside [0, 2^20)^3 or carries a batch index
 //   pcgc_raht_tree        gap i between sorted leaves i and i + 1 is one merge.  One thread per gap: split bit d = msb(key_i ^ key_{i+1}); the
 //                         range [lo, hi] and the two children by binary search on the common prefix (Karras 2012): the keys that share
-//                         key_i's bits above d are a run of the sorted array, so its ends are found in log n probes.  A stable 6-bit radix
-//                         sort of the gaps by 63 - d is the coding order (d descending, gap ascending); a second one with the bit "range
-//                         lies inside one tile" on top lists the gaps that cross a tile boundary first, in the same order.
+//                         key_i's bits above d are a run of the sorted array, so its ends are found in log n probes.  A stable radix
+//                         sort of the gaps by frame * 64 + 63 - d is the coding order (frame, d descending, gap ascending: 6 bits for one
+//                         frame); a second one by 63 - d with the bit "range lies inside one tile" on top lists the gaps that cross a
+//                         tile boundary first, in the same order.
 //   pcgc_raht_forward     node values live in place: the value of a node stands at the first leaf of its range, so a merge reads val[lo]
 //   pcgc_raht_inverse     and val[i + 1] and writes val[lo] (and H[i]); ranges of one split bit are disjoint.  A node depends on nodes of
 //                         lower split bit only.  NOTHING is handed from one workgroup to another inside a launch (no tickets, flags,
@@ -21,6 +22,9 @@
 //   pcgc_raht_quantize    levels, tokens, contexts, escape remainders (compacted behind pcgc_mask_scan) and the [48, 64] histogram
 //   pcgc_raht_dequantize  tokens and escapes -> H^ per gap
 //
+// A SINGLE FRAME IS THE BATCH OF ONE: every step has one kernel and one host body that take `frames`; pcgc_raht_X and pcgc_raht_X_batch are
+// thin entries around it that differ in their argument lists and refusals, and the single ones pass frames = 1 (frame 0 everywhere, no
+// frame boundary, `keys` not read by the quantiser).  Work that exists only for batches sits behind a uniform run-time test.
 // A BATCH of up to RAHT_MAX_FRAMES frames goes through the same steps once (pcgc_raht_*_batch): the frame index is bits
 // 60 .. 63 of the key, so after ONE sort frame b is a run of leaves and every gap with d < 60 lies inside one frame, with the lo / hi /
 // children it has in that frame alone (shifted by the run's start): the searches above compare whole keys.  The B - 1 gaps with d >= 60
@@ -56,20 +60,36 @@ __host__ __device__ static inline uint64_t spread3(uint32_t x) {
     v = (v | (v << 2)) & 0x1249249249249249ull;
     return v;
 }
-// status[1]: bit 0 = a coordinate outside [0, 2^20), bit 1 = a non-zero batch column
-__global__ void __launch_bounds__(256) k_raht_keys(const int4* __restrict__ coords, int64_t n, uint64_t* __restrict__ keys, int32_t* __restrict__ idx,
-                                                   int32_t* status) {
+// One frame is the batch of one: with frames == 1 every row is frame 0 and bits 60 .. 63 of its key are 0.  A row whose batch column lies
+// outside 0 .. frames - 1 raises bit 1 of the flag word and is keyed as frame 0: it neither enters the key nor indexes a counter.
+// dups [frames]: adjacent equal keys per frame (k_raht_dups); rows [frames]: rows per frame, or null where nobody asks (a single frame);
+// flags: bit 0 = a coordinate outside [0, 2^20), bit 1 = a batch index outside 0 .. frames - 1
+__global__ void __launch_bounds__(256) k_raht_keys(const int4* __restrict__ coords, int64_t n, int frames, uint64_t* __restrict__ keys,
+                                                   int32_t* __restrict__ idx, int32_t* rows, int32_t* flags) {
+    __shared__ int32_t cnt[RAHT_MAX_FRAMES];
+    if (rows) {                                                // (uniform)
+        if (threadIdx.x < RAHT_MAX_FRAMES) cnt[threadIdx.x] = 0;
+        __syncthreads();
+    }
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int4 c = coords[i];
-    const int bad = ((((uint32_t)c.y | (uint32_t)c.z | (uint32_t)c.w) >> 20) ? 1 : 0) | (c.x ? 2 : 0);
-    if (bad) atomicOr(status + 1, bad);
-    keys[i] = spread3((uint32_t)c.y) | (spread3((uint32_t)c.z) << 1) | (spread3((uint32_t)c.w) << 2);
-    idx[i] = (int32_t)i;
+    if (i < n) {
+        const int4 c = coords[i];
+        const int bad = ((((uint32_t)c.y | (uint32_t)c.z | (uint32_t)c.w) >> 20) ? 1 : 0) | ((uint32_t)c.x >= (uint32_t)frames ? 2 : 0);
+        if (bad) atomicOr(flags, bad);
+        const uint32_t f = (bad & 2) ? 0u : (uint32_t)c.x;
+        const uint64_t m = spread3((uint32_t)c.y) | (spread3((uint32_t)c.z) << 1) | (spread3((uint32_t)c.w) << 2);
+        keys[i] = (m & ((1ull << RAHT_FRAME_BIT) - 1)) | ((uint64_t)f << RAHT_FRAME_BIT);
+        idx[i] = (int32_t)i;
+        if (rows && !(bad & 2)) atomicAdd(&cnt[f], 1);
+    }
+    if (rows) {
+        __syncthreads();
+        if (threadIdx.x < RAHT_MAX_FRAMES && cnt[threadIdx.x]) atomicAdd(rows + threadIdx.x, cnt[threadIdx.x]);
+    }
 }
-__global__ void __launch_bounds__(256) k_raht_dups(const uint64_t* __restrict__ keys, int64_t n, int32_t* status) {
+__global__ void __launch_bounds__(256) k_raht_dups(const uint64_t* __restrict__ keys, int64_t n, int32_t* dups) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i + 1 < n && keys[i] == keys[i + 1]) atomicAdd(status, 1);
+    if (i + 1 < n && keys[i] == keys[i + 1]) atomicAdd(dups + (int)(keys[i] >> RAHT_FRAME_BIT), 1);      // (< frames: k_raht_keys wrote the key)
 }
 
 template <typename K>
@@ -80,78 +100,50 @@ static size_t sort_temp_bytes(int64_t n, int bits) {
     return tmp;
 }
 
-extern "C" size_t pcgc_raht_keys_workspace_bytes(int64_t n) {
+// The entries below are thin: each checks what is its own to check under its own name (`who`, as PCGC_REQUIRE would print it), then calls
+// the one implementation of its step, which takes `frames`.  who + 5 is the name without "pcgc_", as the launch errors print it.
+#define RAHT_REQUIRE(who, cond, msg) do { if (!(cond)) { pcgc_set_error("%s: %s", who, msg); return -2; } } while (0)
+#define RAHT_CHECK_HIP(who, e) do { if ((e) != hipSuccess) { pcgc_set_error("%s: %s", (who) + 5, hipGetErrorString(e)); return -1; } } while (0)
+
+// sort_bits: the sort's end bit, 60 for the single entry and 64 for the batch's (unsigned: frames 8 .. 15 set bit 63)
+static size_t keys_workspace_bytes(int64_t n, int sort_bits) {
     if (n < 1) n = 1;
-    return align256((size_t)n * 8) + align256((size_t)n * 4) + align256(sort_temp_bytes<uint64_t>(n, 60));
+    return align256((size_t)n * 8) + align256((size_t)n * 4) + align256(sort_temp_bytes<uint64_t>(n, sort_bits));
 }
+// status: status_ints ints, zeroed here; dups = status [frames], rows and flags point into it
+static int raht_keys(const char* who, const int32_t* coords, int64_t n, int frames, int sort_bits, uint64_t* keys, int32_t* perm, int32_t* status,
+                     int status_ints, int32_t* rows, int32_t* flags, void* workspace, size_t workspace_bytes, hipStream_t s) {
+    RAHT_REQUIRE(who, n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
+    RAHT_REQUIRE(who, frames >= 1 && frames <= RAHT_MAX_FRAMES, "1 to 16 frames");
+    RAHT_REQUIRE(who, coords && keys && perm && status && workspace, "null argument");
+    RAHT_REQUIRE(who, workspace_bytes >= keys_workspace_bytes(n, sort_bits), "workspace too small");
+    char* ws = (char*)workspace;
+    uint64_t* kin = (uint64_t*)ws; ws += align256((size_t)n * 8);
+    int32_t* idx = (int32_t*)ws; ws += align256((size_t)n * 4);
+    size_t tmp = sort_temp_bytes<uint64_t>(n, sort_bits);
+    hipError_t e = hipMemsetAsync(status, 0, status_ints * sizeof(int32_t), s);
+    RAHT_CHECK_HIP(who, e);
+    hipLaunchKernelGGL(k_raht_keys, dim3(grid_for(n, 256)), dim3(256), 0, s, (const int4*)coords, n, frames, kin, idx, rows, flags);
+    PCGC_CHECK_LAUNCH(who + 5);
+    e = rocprim::radix_sort_pairs((void*)ws, tmp, kin, keys, idx, perm, (size_t)n, 0, sort_bits, s);
+    RAHT_CHECK_HIP(who, e);
+    hipLaunchKernelGGL(k_raht_dups, dim3(grid_for(n, 256)), dim3(256), 0, s, keys, n, status);
+    PCGC_CHECK_LAUNCH(who + 5);
+    return 0;
+}
+// status [2]: adjacent equal keys, then the flag word (bit 1: a non-zero batch column)
+extern "C" size_t pcgc_raht_keys_workspace_bytes(int64_t n) { return keys_workspace_bytes(n, RAHT_FRAME_BIT); }
 extern "C" int pcgc_raht_keys(const int32_t* coords, int64_t n, uint64_t* keys, int32_t* perm, int32_t* status, void* workspace,
                               size_t workspace_bytes, void* stream) {
-    PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
-    PCGC_REQUIRE(coords && keys && perm && status && workspace, "null argument");
-    PCGC_REQUIRE(workspace_bytes >= pcgc_raht_keys_workspace_bytes(n), "workspace too small");
-    char* ws = (char*)workspace;
-    uint64_t* kin = (uint64_t*)ws; ws += align256((size_t)n * 8);
-    int32_t* idx = (int32_t*)ws; ws += align256((size_t)n * 4);
-    size_t tmp = sort_temp_bytes<uint64_t>(n, 60);
-    hipError_t e = hipMemsetAsync(status, 0, 2 * sizeof(int32_t), S(stream));
-    if (e != hipSuccess) { pcgc_set_error("raht_keys: %s", hipGetErrorString(e)); return -1; }
-    hipLaunchKernelGGL(k_raht_keys, dim3(grid_for(n, 256)), dim3(256), 0, S(stream), (const int4*)coords, n, kin, idx, status);
-    PCGC_CHECK_LAUNCH("raht_keys");
-    e = rocprim::radix_sort_pairs((void*)ws, tmp, kin, keys, idx, perm, (size_t)n, 0, 60, S(stream));
-    if (e != hipSuccess) { pcgc_set_error("raht_keys: %s", hipGetErrorString(e)); return -1; }
-    hipLaunchKernelGGL(k_raht_dups, dim3(grid_for(n, 256)), dim3(256), 0, S(stream), keys, n, status);
-    PCGC_CHECK_LAUNCH("raht_keys");
-    return 0;
+    return raht_keys(__func__, coords, n, 1, RAHT_FRAME_BIT, keys, perm, status, 2, nullptr, status ? status + 1 : nullptr, workspace, workspace_bytes,
+                     S(stream));
 }
-
-// status [34]: [0 .. 15] adjacent equal keys per frame, [16 .. 31] rows per frame, [32] bit 0 = a coordinate outside [0, 2^20), bit 1 = a frame
-// index outside 0 .. B - 1
-__global__ void __launch_bounds__(256) k_raht_keys_batch(const int4* __restrict__ coords, int64_t n, int B, uint64_t* __restrict__ keys,
-                                                         int32_t* __restrict__ idx, int32_t* status) {
-    __shared__ int32_t cnt[RAHT_MAX_FRAMES];
-    if (threadIdx.x < RAHT_MAX_FRAMES) cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        const int4 c = coords[i];
-        const int bad = ((((uint32_t)c.y | (uint32_t)c.z | (uint32_t)c.w) >> 20) ? 1 : 0) | ((uint32_t)c.x >= (uint32_t)B ? 2 : 0);
-        if (bad) atomicOr(status + 32, bad);
-        const uint32_t f = (uint32_t)c.x & (RAHT_MAX_FRAMES - 1);
-        const uint64_t m = spread3((uint32_t)c.y) | (spread3((uint32_t)c.z) << 1) | (spread3((uint32_t)c.w) << 2);
-        keys[i] = (m & ((1ull << RAHT_FRAME_BIT) - 1)) | ((uint64_t)f << RAHT_FRAME_BIT);
-        idx[i] = (int32_t)i;
-        if (!(bad & 2)) atomicAdd(&cnt[f], 1);
-    }
-    __syncthreads();
-    if (threadIdx.x < RAHT_MAX_FRAMES && cnt[threadIdx.x]) atomicAdd(status + 16 + threadIdx.x, cnt[threadIdx.x]);
-}
-__global__ void __launch_bounds__(256) k_raht_dups_batch(const uint64_t* __restrict__ keys, int64_t n, int32_t* status) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i + 1 < n && keys[i] == keys[i + 1]) atomicAdd(status + (int)(keys[i] >> RAHT_FRAME_BIT), 1);
-}
-extern "C" int64_t pcgc_raht_keys_batch_workspace_bytes(int64_t n) {
-    if (n < 1) n = 1;
-    return (int64_t)(align256((size_t)n * 8) + align256((size_t)n * 4) + align256(sort_temp_bytes<uint64_t>(n, 64)));
-}
+// status [34]: [0 .. 15] adjacent equal keys per frame, [16 .. 31] rows per frame, [32] the flag word
+extern "C" int64_t pcgc_raht_keys_batch_workspace_bytes(int64_t n) { return (int64_t)keys_workspace_bytes(n, 64); }
 extern "C" int pcgc_raht_keys_batch(const int32_t* coords, int64_t n, int frames, uint64_t* keys, int32_t* perm, int32_t* status, void* workspace,
                                     size_t workspace_bytes, void* stream) {
-    PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
-    PCGC_REQUIRE(frames >= 1 && frames <= RAHT_MAX_FRAMES, "1 to 16 frames");
-    PCGC_REQUIRE(coords && keys && perm && status && workspace, "null argument");
-    PCGC_REQUIRE(workspace_bytes >= (size_t)pcgc_raht_keys_batch_workspace_bytes(n), "workspace too small");
-    char* ws = (char*)workspace;
-    uint64_t* kin = (uint64_t*)ws; ws += align256((size_t)n * 8);
-    int32_t* idx = (int32_t*)ws; ws += align256((size_t)n * 4);
-    size_t tmp = sort_temp_bytes<uint64_t>(n, 64);
-    hipError_t e = hipMemsetAsync(status, 0, 34 * sizeof(int32_t), S(stream));
-    if (e != hipSuccess) { pcgc_set_error("raht_keys_batch: %s", hipGetErrorString(e)); return -1; }
-    hipLaunchKernelGGL(k_raht_keys_batch, dim3(grid_for(n, 256)), dim3(256), 0, S(stream), (const int4*)coords, n, frames, kin, idx, status);
-    PCGC_CHECK_LAUNCH("raht_keys_batch");
-    e = rocprim::radix_sort_pairs((void*)ws, tmp, kin, keys, idx, perm, (size_t)n, 0, 64, S(stream));      // (unsigned: frames 8 .. 15 set bit 63)
-    if (e != hipSuccess) { pcgc_set_error("raht_keys_batch: %s", hipGetErrorString(e)); return -1; }
-    hipLaunchKernelGGL(k_raht_dups_batch, dim3(grid_for(n, 256)), dim3(256), 0, S(stream), keys, n, status);
-    PCGC_CHECK_LAUNCH("raht_keys_batch");
-    return 0;
+    return raht_keys(__func__, coords, n, frames, 64, keys, perm, status, 34, status ? status + RAHT_MAX_FRAMES : nullptr,
+                     status ? status + 2 * RAHT_MAX_FRAMES : nullptr, workspace, workspace_bytes, S(stream));
 }
 
 // ------------------------------------------------------------------------------------------------------------------ tree
@@ -183,33 +175,49 @@ __device__ static inline void tree_gap(const uint64_t* __restrict__ keys, int64_
     }
 }
 
-// cnt [128]: gaps per split bit, all (0 .. 63) and those whose range crosses a tile boundary (64 .. 127)
-__global__ void __launch_bounds__(256) k_raht_tree(const uint64_t* __restrict__ keys, int64_t n, int32_t tile, uint8_t* __restrict__ d8,
+// cnt [(frames + 1) x 64]: gaps per frame and split bit, then (row `frames`) those of all frames whose range crosses a tile boundary.  The LDS
+// array has the size of the largest batch; only the used rows are zeroed and flushed (128 counters for a single frame).
+// A frame boundary (frames > 1 and d >= 60) is no merge: lo = hi = -1, no children, counted nowhere, sorted behind everything.
+// K: the type of the coding order's sort key, frame * 64 + 63 - d: uint8_t holds it for a single frame, a batch needs uint16_t.
+#define RAHT_CNT_MAX ((RAHT_MAX_FRAMES + 1) * 64)
+template <typename K>
+__global__ void __launch_bounds__(256) k_raht_tree(const uint64_t* __restrict__ keys, int64_t n, int frames, int32_t tile, uint8_t* __restrict__ d8,
                                                    int32_t* __restrict__ lo_o, int32_t* __restrict__ hi_o, int32_t* __restrict__ left_o,
-                                                   int32_t* __restrict__ right_o, uint8_t* __restrict__ skey, uint8_t* __restrict__ skey_cross,
+                                                   int32_t* __restrict__ right_o, K* __restrict__ skey, uint8_t* __restrict__ skey_cross,
                                                    int32_t* __restrict__ idx, int32_t* cnt) {
-    __shared__ int32_t h[128];
-    if (threadIdx.x < 128) h[threadIdx.x] = 0;
+    __shared__ int32_t h[RAHT_CNT_MAX];
+    const int used = (frames + 1) * 64;
+    for (int j = threadIdx.x; j < used; j += 256) h[j] = 0;
     __syncthreads();
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g < n - 1) {
         const int d = msb64((keys[g] ^ keys[g + 1]) | 1ull);   // (| 1: equal keys are refused by the caller; this keeps the shifts defined)
-        int64_t lo, hi;
-        int32_t left, right;
-        tree_gap(keys, n, g, d, lo, hi, left, right);
-        const int cross = (lo / tile) != (hi / tile);
-        d8[g] = (uint8_t)d; lo_o[g] = (int32_t)lo; hi_o[g] = (int32_t)hi; left_o[g] = left; right_o[g] = right;
-        skey[g] = (uint8_t)(63 - d); skey_cross[g] = (uint8_t)((63 - d) | (cross ? 0 : 64));
         idx[g] = (int32_t)g;
-        atomicAdd(&h[d], 1);
-        if (cross) atomicAdd(&h[64 + d], 1);
+        d8[g] = (uint8_t)d;
+        if (frames > 1 && d >= RAHT_FRAME_BIT) {
+            lo_o[g] = -1; hi_o[g] = -1; left_o[g] = ~(int32_t)g; right_o[g] = ~(int32_t)(g + 1);
+            skey[g] = (K)(RAHT_MAX_FRAMES * 64); skey_cross[g] = 128;
+        } else {
+            int64_t lo, hi;
+            int32_t left, right;
+            tree_gap(keys, n, g, d, lo, hi, left, right);
+            const int cross = (lo / tile) != (hi / tile);
+            const int f = frames > 1 ? (int)(keys[g] >> RAHT_FRAME_BIT) : 0;
+            lo_o[g] = (int32_t)lo; hi_o[g] = (int32_t)hi; left_o[g] = left; right_o[g] = right;
+            skey[g] = (K)(f * 64 + 63 - d); skey_cross[g] = (uint8_t)((63 - d) | (cross ? 0 : 64));
+            if (f < frames) {                                  // (always, for keys pcgc_raht_keys wrote)
+                atomicAdd(&h[f * 64 + d], 1);
+                if (cross) atomicAdd(&h[frames * 64 + d], 1);
+            }
+        }
     }
     __syncthreads();
-    if (threadIdx.x < 128 && h[threadIdx.x]) atomicAdd(cnt + threadIdx.x, h[threadIdx.x]);
+    for (int j = threadIdx.x; j < used; j += 256) if (h[j]) atomicAdd(cnt + j, h[j]);
 }
-// offsets [130]: bucket[65] then cross[65]; the gaps of split bit d are list[off[63 - d] .. off[64 - d])
-__global__ void k_raht_offsets(const int32_t* __restrict__ cnt, int32_t* __restrict__ offsets) {
-    if (threadIdx.x < 2) {
+// offsets [(frames + 1) x 65]: bucket [65] of every frame (counted from the frame's own first gap), then cross [65] of all frames; the gaps
+// of split bit d are list[off[63 - d] .. off[64 - d]).  A single frame: bucket [65], then cross [65].
+__global__ void k_raht_offsets(const int32_t* __restrict__ cnt, int frames, int32_t* __restrict__ offsets) {
+    if ((int)threadIdx.x <= frames) {
         const int32_t* c = cnt + 64 * threadIdx.x;
         int32_t* o = offsets + 65 * threadIdx.x;
         int32_t acc = 0;
@@ -218,122 +226,67 @@ __global__ void k_raht_offsets(const int32_t* __restrict__ cnt, int32_t* __restr
     }
 }
 
-extern "C" size_t pcgc_raht_tree_workspace_bytes(int64_t n) {
+// the two sorts run one after the other and share their temporary storage
+template <typename K>
+static size_t tree_sort_temp_bytes(size_t g, int order_bits, int cross_bits) {
+    const size_t a = sort_temp_bytes<K>((int64_t)g, order_bits), b = sort_temp_bytes<uint8_t>((int64_t)g, cross_bits);
+    return a > b ? a : b;
+}
+template <typename K>
+static size_t tree_workspace_bytes(int64_t n, int frames, int order_bits, int cross_bits) {
     const size_t g = (size_t)(n < 2 ? 1 : n - 1);
-    return 3 * align256(g) + align256(g * 4) + 512 + align256(sort_temp_bytes<uint8_t>((int64_t)g, 7));
+    return 2 * align256(g * sizeof(K)) + 2 * align256(g) + align256(g * 4) + align256((size_t)(frames + 1) * 64 * 4) +
+           align256(tree_sort_temp_bytes<K>(g, order_bits, cross_bits));
 }
-extern "C" int pcgc_raht_tree(const uint64_t* keys, int64_t n, uint8_t* d, int32_t* lo, int32_t* hi, int32_t* left, int32_t* right,
-                              int32_t* order, int32_t* cross_order, int32_t* offsets, void* workspace, size_t workspace_bytes, void* stream) {
-    PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
-    PCGC_REQUIRE(offsets && workspace, "null argument");
-    PCGC_REQUIRE(workspace_bytes >= pcgc_raht_tree_workspace_bytes(n), "workspace too small");
+// order_bits, cross_bits: the end bits of the two sorts (6 and 7 for the single entry, 11 and 8 for the batch's); sized: what the entry's own
+// sizing call answers, at least tree_workspace_bytes<K>(n, frames, ..)
+template <typename K>
+static int raht_tree(const char* who, const uint64_t* keys, int64_t n, int frames, int order_bits, int cross_bits, uint8_t* d, int32_t* lo,
+                     int32_t* hi, int32_t* left, int32_t* right, int32_t* order, int32_t* cross_order, int32_t* offsets, void* workspace,
+                     size_t workspace_bytes, size_t sized, hipStream_t s) {
+    RAHT_REQUIRE(who, n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
+    RAHT_REQUIRE(who, frames >= 1 && frames <= RAHT_MAX_FRAMES && (frames == 1 || sizeof(K) > 1), "1 to 16 frames");
+    RAHT_REQUIRE(who, offsets && workspace, "null argument");
+    RAHT_REQUIRE(who, workspace_bytes >= sized, "workspace too small");
     const int64_t g = n - 1;
+    const size_t g1 = (size_t)(g < 1 ? 1 : g), cnt_bytes = (size_t)(frames + 1) * 64 * 4;
     char* ws = (char*)workspace;
-    uint8_t* skey = (uint8_t*)ws; ws += align256((size_t)(g < 1 ? 1 : g));
-    uint8_t* skey_cross = (uint8_t*)ws; ws += align256((size_t)(g < 1 ? 1 : g));
-    uint8_t* sorted = (uint8_t*)ws; ws += align256((size_t)(g < 1 ? 1 : g));
-    int32_t* idx = (int32_t*)ws; ws += align256((size_t)(g < 1 ? 1 : g) * 4);
-    int32_t* cnt = (int32_t*)ws; ws += 512;
-    hipError_t e = hipMemsetAsync(cnt, 0, 512, S(stream));
-    if (e != hipSuccess) { pcgc_set_error("raht_tree: %s", hipGetErrorString(e)); return -1; }
-    if (g > 0) {
-        PCGC_REQUIRE(keys && d && lo && hi && left && right && order && cross_order, "null argument");
-        hipLaunchKernelGGL(k_raht_tree, dim3(grid_for(g, 256)), dim3(256), 0, S(stream), keys, n, (int32_t)RAHT_TILE, d, lo, hi, left, right, skey,
-                           skey_cross, idx, cnt);
-        PCGC_CHECK_LAUNCH("raht_tree");
-        size_t tmp = sort_temp_bytes<uint8_t>(g, 7);
-        e = rocprim::radix_sort_pairs((void*)ws, tmp, skey, sorted, idx, order, (size_t)g, 0, 6, S(stream));
-        if (e == hipSuccess) e = rocprim::radix_sort_pairs((void*)ws, tmp, skey_cross, sorted, idx, cross_order, (size_t)g, 0, 7, S(stream));
-        if (e != hipSuccess) { pcgc_set_error("raht_tree: %s", hipGetErrorString(e)); return -1; }
-    }
-    hipLaunchKernelGGL(k_raht_offsets, dim3(1), dim3(64), 0, S(stream), cnt, offsets);
-    PCGC_CHECK_LAUNCH("raht_tree");
-    return 0;
-}
-
-// The tree of a batch.  cnt [17 x 64]: gaps per frame and split bit, then (row 16) those of all frames whose range crosses a tile boundary.
-// A frame boundary (d >= 60) is no merge: lo = hi = -1, no children, counted nowhere, sorted behind everything.
-#define RAHT_BATCH_CNT ((RAHT_MAX_FRAMES + 1) * 64)
-__global__ void __launch_bounds__(256) k_raht_tree_batch(const uint64_t* __restrict__ keys, int64_t n, int32_t tile, uint8_t* __restrict__ d8,
-                                                         int32_t* __restrict__ lo_o, int32_t* __restrict__ hi_o, int32_t* __restrict__ left_o,
-                                                         int32_t* __restrict__ right_o, uint16_t* __restrict__ skey,
-                                                         uint8_t* __restrict__ skey_cross, int32_t* __restrict__ idx, int32_t* cnt) {
-    __shared__ int32_t h[RAHT_BATCH_CNT];
-    for (int j = threadIdx.x; j < RAHT_BATCH_CNT; j += 256) h[j] = 0;
-    __syncthreads();
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g < n - 1) {
-        const int d = msb64((keys[g] ^ keys[g + 1]) | 1ull);
-        idx[g] = (int32_t)g;
-        d8[g] = (uint8_t)d;
-        if (d >= RAHT_FRAME_BIT) {
-            lo_o[g] = -1; hi_o[g] = -1; left_o[g] = ~(int32_t)g; right_o[g] = ~(int32_t)(g + 1);
-            skey[g] = (uint16_t)(RAHT_MAX_FRAMES * 64); skey_cross[g] = 128;
-        } else {
-            int64_t lo, hi;
-            int32_t left, right;
-            tree_gap(keys, n, g, d, lo, hi, left, right);
-            const int cross = (lo / tile) != (hi / tile);
-            const int f = (int)(keys[g] >> RAHT_FRAME_BIT);
-            lo_o[g] = (int32_t)lo; hi_o[g] = (int32_t)hi; left_o[g] = left; right_o[g] = right;
-            skey[g] = (uint16_t)(f * 64 + 63 - d); skey_cross[g] = (uint8_t)((63 - d) | (cross ? 0 : 64));
-            atomicAdd(&h[f * 64 + d], 1);
-            if (cross) atomicAdd(&h[RAHT_MAX_FRAMES * 64 + d], 1);
-        }
-    }
-    __syncthreads();
-    for (int j = threadIdx.x; j < RAHT_BATCH_CNT; j += 256) if (h[j]) atomicAdd(cnt + j, h[j]);
-}
-// offsets [(frames + 1) x 65]: bucket [65] of every frame (counted from the frame's own first gap), then cross [65] of the batch
-__global__ void k_raht_offsets_batch(const int32_t* __restrict__ cnt, int frames, int32_t* __restrict__ offsets) {
-    if ((int)threadIdx.x <= frames) {
-        const int32_t* c = cnt + 64 * ((int)threadIdx.x < frames ? threadIdx.x : RAHT_MAX_FRAMES);
-        int32_t* o = offsets + 65 * threadIdx.x;
-        int32_t acc = 0;
-        for (int b = 0; b < 64; ++b) { o[b] = acc; acc += c[63 - b]; }
-        o[64] = acc;
-    }
-}
-
-extern "C" int64_t pcgc_raht_tree_batch_workspace_bytes(int64_t n) {
-    const size_t g = (size_t)(n < 2 ? 1 : n - 1);
-    return (int64_t)(2 * align256(g * 2) + 2 * align256(g) + align256(g * 4) + align256(RAHT_BATCH_CNT * 4) +
-                     align256(sort_temp_bytes<uint16_t>((int64_t)g, 11)) + align256(sort_temp_bytes<uint8_t>((int64_t)g, 8)));
-}
-extern "C" int pcgc_raht_tree_batch(const uint64_t* keys, int64_t n, int frames, uint8_t* d, int32_t* lo, int32_t* hi, int32_t* left, int32_t* right,
-                                    int32_t* order, int32_t* cross_order, int32_t* offsets, void* workspace, size_t workspace_bytes,
-                                    void* stream) {
-    PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
-    PCGC_REQUIRE(frames >= 1 && frames <= RAHT_MAX_FRAMES, "1 to 16 frames");
-    PCGC_REQUIRE(offsets && workspace, "null argument");
-    PCGC_REQUIRE(workspace_bytes >= (size_t)pcgc_raht_tree_batch_workspace_bytes(n), "workspace too small");
-    const int64_t g = n - 1;
-    const size_t g1 = (size_t)(g < 1 ? 1 : g);
-    char* ws = (char*)workspace;
-    uint16_t* skey = (uint16_t*)ws; ws += align256(g1 * 2);
-    uint16_t* sorted = (uint16_t*)ws; ws += align256(g1 * 2);
+    K* skey = (K*)ws; ws += align256(g1 * sizeof(K));
+    K* sorted = (K*)ws; ws += align256(g1 * sizeof(K));
     uint8_t* skey_cross = (uint8_t*)ws; ws += align256(g1);
     uint8_t* sorted_cross = (uint8_t*)ws; ws += align256(g1);
     int32_t* idx = (int32_t*)ws; ws += align256(g1 * 4);
-    int32_t* cnt = (int32_t*)ws; ws += align256(RAHT_BATCH_CNT * 4);
-    hipError_t e = hipMemsetAsync(cnt, 0, RAHT_BATCH_CNT * 4, S(stream));
-    if (e != hipSuccess) { pcgc_set_error("raht_tree_batch: %s", hipGetErrorString(e)); return -1; }
+    int32_t* cnt = (int32_t*)ws; ws += align256(cnt_bytes);
+    hipError_t e = hipMemsetAsync(cnt, 0, cnt_bytes, s);
+    RAHT_CHECK_HIP(who, e);
     if (g > 0) {
-        PCGC_REQUIRE(keys && d && lo && hi && left && right && order && cross_order, "null argument");
-        hipLaunchKernelGGL(k_raht_tree_batch, dim3(grid_for(g, 256)), dim3(256), 0, S(stream), keys, n, (int32_t)RAHT_TILE, d, lo, hi, left, right,
-                           skey, skey_cross, idx, cnt);
-        PCGC_CHECK_LAUNCH("raht_tree_batch");
-        size_t tmp = sort_temp_bytes<uint16_t>(g, 11);
-        e = rocprim::radix_sort_pairs((void*)ws, tmp, skey, sorted, idx, order, (size_t)g, 0, 11, S(stream));
-        ws += align256(tmp);
-        tmp = sort_temp_bytes<uint8_t>(g, 8);
-        if (e == hipSuccess) e = rocprim::radix_sort_pairs((void*)ws, tmp, skey_cross, sorted_cross, idx, cross_order, (size_t)g, 0, 8, S(stream));
-        if (e != hipSuccess) { pcgc_set_error("raht_tree_batch: %s", hipGetErrorString(e)); return -1; }
+        RAHT_REQUIRE(who, keys && d && lo && hi && left && right && order && cross_order, "null argument");
+        hipLaunchKernelGGL(k_raht_tree<K>, dim3(grid_for(g, 256)), dim3(256), 0, s, keys, n, frames, (int32_t)RAHT_TILE, d, lo, hi, left, right, skey,
+                           skey_cross, idx, cnt);
+        PCGC_CHECK_LAUNCH(who + 5);
+        size_t tmp = tree_sort_temp_bytes<K>(g1, order_bits, cross_bits);
+        e = rocprim::radix_sort_pairs((void*)ws, tmp, skey, sorted, idx, order, (size_t)g, 0, order_bits, s);
+        if (e == hipSuccess) e = rocprim::radix_sort_pairs((void*)ws, tmp, skey_cross, sorted_cross, idx, cross_order, (size_t)g, 0, cross_bits, s);
+        RAHT_CHECK_HIP(who, e);
     }
-    hipLaunchKernelGGL(k_raht_offsets_batch, dim3(1), dim3(64), 0, S(stream), cnt, frames, offsets);
-    PCGC_CHECK_LAUNCH("raht_tree_batch");
+    hipLaunchKernelGGL(k_raht_offsets, dim3(1), dim3(64), 0, s, (const int32_t*)cnt, frames, offsets);
+    PCGC_CHECK_LAUNCH(who + 5);
     return 0;
 }
+extern "C" size_t pcgc_raht_tree_workspace_bytes(int64_t n) { return tree_workspace_bytes<uint8_t>(n, 1, 6, 7); }
+extern "C" int pcgc_raht_tree(const uint64_t* keys, int64_t n, uint8_t* d, int32_t* lo, int32_t* hi, int32_t* left, int32_t* right,
+                              int32_t* order, int32_t* cross_order, int32_t* offsets, void* workspace, size_t workspace_bytes, void* stream) {
+    return raht_tree<uint8_t>(__func__, keys, n, 1, 6, 7, d, lo, hi, left, right, order, cross_order, offsets, workspace, workspace_bytes,
+                              pcgc_raht_tree_workspace_bytes(n), S(stream));
+}
+extern "C" int64_t pcgc_raht_tree_batch_workspace_bytes(int64_t n) { return (int64_t)tree_workspace_bytes<uint16_t>(n, RAHT_MAX_FRAMES, 11, 8); }
+extern "C" int pcgc_raht_tree_batch(const uint64_t* keys, int64_t n, int frames, uint8_t* d, int32_t* lo, int32_t* hi, int32_t* left, int32_t* right,
+                                    int32_t* order, int32_t* cross_order, int32_t* offsets, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+    return raht_tree<uint16_t>(__func__, keys, n, frames, 11, 8, d, lo, hi, left, right, order, cross_order, offsets, workspace, workspace_bytes,
+                               (size_t)pcgc_raht_tree_batch_workspace_bytes(n), S(stream));
+}
+
 
 // ------------------------------------------------------------------------------------------------------------------ colour space, lifting
 __device__ static inline i3 ycocg_fwd(const uint8_t* __restrict__ rgb, int64_t row) {
@@ -515,89 +468,35 @@ __global__ void __launch_bounds__(RAHT_THREADS) k_raht_tile(const uint8_t* __res
     }
 }
 
-// offsets [65] on the HOST: ascending, within [0, n - 1]
-static bool offsets_sound(const int32_t* off, int64_t n) {
-    if (off[0] != 0) return false;
-    for (int b = 0; b < 64; ++b) if (off[b + 1] < off[b]) return false;
-    return off[64] <= n - 1;
-}
-
-template <bool FWD>
-static int raht_run(const uint8_t* rgb_in, uint8_t* rgb_out, const int32_t* perm, int64_t n, const uint8_t* d, const int32_t* lo, const int32_t* hi,
-                    const int32_t* order, const int32_t* bucket_off, const int32_t* cross_order, const int32_t* cross_off_dev, int form, i3 dc,
-                    i3* val, i3* H, hipStream_t s) {
-    const unsigned tiles = grid_for(n, RAHT_TILE);
-    if (!FWD) hipLaunchKernelGGL(k_raht_set_dc, dim3(1), dim3(64), 0, s, val, dc);
-    if (form == 0) {
-        if (FWD) hipLaunchKernelGGL(k_raht_load, dim3(grid_for(n, 256)), dim3(256), 0, s, rgb_in, perm, n, val);
-        for (int k = 0; k < 64; ++k) {
-            const int b = FWD ? 63 - k : k;
-            const int64_t begin = bucket_off[b], end = bucket_off[b + 1];
-            if (begin < end)
-                hipLaunchKernelGGL(k_raht_bit<FWD>, dim3(grid_for(end - begin, 256)), dim3(256), 0, s, order, begin, end, n, lo, hi, val, H);
-        }
-        if (!FWD) hipLaunchKernelGGL(k_raht_store, dim3(grid_for(n, 256)), dim3(256), 0, s, val, perm, n, rgb_out);
-    } else {
-        if (FWD) hipLaunchKernelGGL(k_raht_tile<true>, dim3(tiles), dim3(RAHT_THREADS), 0, s, rgb_in, rgb_out, perm, n, d, lo, hi, val, H);
-        if (tiles > 1)
-            hipLaunchKernelGGL(k_raht_spine<FWD>, dim3(1), dim3(RAHT_SPINE_THREADS), 0, s, cross_order, cross_off_dev, n, lo, hi, val, H);
-        if (!FWD) hipLaunchKernelGGL(k_raht_tile<false>, dim3(tiles), dim3(RAHT_THREADS), 0, s, rgb_in, rgb_out, perm, n, d, lo, hi, val, H);
+// `sets` groups of 65 offsets on the HOST, one behind the other in one list: each ascending, each starting where the one before ends, all
+// within [0, n - 1]
+static bool offsets_sound(const int32_t* off, int sets, int64_t n) {
+    int32_t at = 0;
+    for (int set = 0; set < sets; ++set) {
+        if (off[65 * set] != at) return false;
+        for (int b = 0; b < 64; ++b) if (off[65 * set + b + 1] < off[65 * set + b]) return false;
+        at = off[65 * set + 64];
     }
-    return 0;
+    return at <= n - 1;
 }
 
-extern "C" int pcgc_raht_forward(const uint8_t* rgb, const int32_t* perm, int64_t n, const uint8_t* d, const int32_t* lo, const int32_t* hi,
-                                 const int32_t* order, const int32_t* bucket_off, const int32_t* cross_order, const int32_t* cross_off, int form,
-                                 int32_t* val, int32_t* H, void* stream) {
-    PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
-    PCGC_REQUIRE(form == 0 || form == 1, "form 0 (one launch per split bit) or 1 (tiles)");
-    PCGC_REQUIRE(rgb && perm && val && bucket_off && cross_off, "null argument");
-    PCGC_REQUIRE(n == 1 || (d && lo && hi && order && cross_order && H), "null argument");
-    PCGC_REQUIRE(offsets_sound(bucket_off, n), "bucket offsets are not those of a tree of n leaves");
-    raht_run<true>(rgb, nullptr, perm, n, d, lo, hi, order, bucket_off, cross_order, cross_off, form, i3{0, 0, 0}, (i3*)val, (i3*)H, S(stream));
-    PCGC_CHECK_LAUNCH("raht_forward");
-    return 0;
-}
-extern "C" int pcgc_raht_inverse(const int32_t* Hhat, int32_t dc_y, int32_t dc_co, int32_t dc_cg, const int32_t* perm, int64_t n, const uint8_t* d,
-                                 const int32_t* lo, const int32_t* hi, const int32_t* order, const int32_t* bucket_off,
-                                 const int32_t* cross_order, const int32_t* cross_off, int form, int32_t* val, uint8_t* rgb, void* stream) {
-    PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
-    PCGC_REQUIRE(form == 0 || form == 1, "form 0 (one launch per split bit) or 1 (tiles)");
-    PCGC_REQUIRE(rgb && perm && val && bucket_off && cross_off, "null argument");
-    PCGC_REQUIRE(n == 1 || (d && lo && hi && order && cross_order && Hhat), "null argument");
-    PCGC_REQUIRE(offsets_sound(bucket_off, n), "bucket offsets are not those of a tree of n leaves");
-    raht_run<false>(nullptr, rgb, perm, n, d, lo, hi, order, bucket_off, cross_order, cross_off, form, i3{dc_y, dc_co, dc_cg}, (i3*)val,
-                    (i3*)const_cast<int32_t*>(Hhat), S(stream));
-    PCGC_CHECK_LAUNCH("raht_inverse");
-    return 0;
-}
-
-// A batch.  The kernels are the ones above: a frame boundary has lo = hi = -1, so the tile kernel does not take it (l >= s fails), it is in
-// no list the other two walk, and ranges of one split bit are disjoint across frames as they are inside one.  Form 0 walks cross_order,
-// which lists every split bit twice (the crossing gaps, then the others): bit_off [130] on the HOST holds both sets of 65 offsets.
-__global__ void k_raht_set_dc_batch(i3* val, int64_t n, const int32_t* __restrict__ starts, const i3* __restrict__ dc, int frames) {
-    const int b = threadIdx.x;
-    if (b < frames && starts[b] >= 0 && starts[b] < n) val[starts[b]] = dc[b];
-}
-static bool bit_offsets_sound(const int32_t* off, int64_t n) {
-    if (off[0] != 0 || off[65] != off[64]) return false;
-    for (int b = 0; b < 64; ++b) if (off[b + 1] < off[b] || off[65 + b + 1] < off[65 + b]) return false;
-    return off[129] <= n - 1;
-}
+// One transform for one frame or a batch: a frame boundary has lo = hi = -1, so the tile kernel does not take it (l >= s fails), it is in no
+// list the other two walk, and ranges of one split bit are disjoint across frames as they are inside one.  Form 0 walks `list` by `sets`
+// groups of 65 host offsets per split bit: a single frame's coding order under its bucket offsets (one group), or a batch's cross_order,
+// which lists every split bit twice (the crossing gaps, then the others: two groups).  The DCs of the inverse are set by the caller.
 template <bool FWD>
-static int raht_run_batch(const uint8_t* rgb_in, uint8_t* rgb_out, const int32_t* perm, int64_t n, const uint8_t* d, const int32_t* lo,
-                          const int32_t* hi, const int32_t* cross_order, const int32_t* bit_off, const int32_t* cross_off_dev, int form,
-                          const int32_t* starts, const i3* dc, int frames, i3* val, i3* H, hipStream_t s) {
+static void raht_run(const uint8_t* rgb_in, uint8_t* rgb_out, const int32_t* perm, int64_t n, const uint8_t* d, const int32_t* lo, const int32_t* hi,
+                     const int32_t* list, const int32_t* off, int sets, const int32_t* cross_order, const int32_t* cross_off_dev, int form, i3* val,
+                     i3* H, hipStream_t s) {
     const unsigned tiles = grid_for(n, RAHT_TILE);
-    if (!FWD) hipLaunchKernelGGL(k_raht_set_dc_batch, dim3(1), dim3(64), 0, s, val, n, starts, dc, frames);
     if (form == 0) {
         if (FWD) hipLaunchKernelGGL(k_raht_load, dim3(grid_for(n, 256)), dim3(256), 0, s, rgb_in, perm, n, val);
         for (int k = 0; k < 64; ++k) {
             const int b = FWD ? 63 - k : k;
-            for (int half = 0; half < 2; ++half) {
-                const int64_t begin = bit_off[65 * half + b], end = bit_off[65 * half + b + 1];
+            for (int set = 0; set < sets; ++set) {
+                const int64_t begin = off[65 * set + b], end = off[65 * set + b + 1];
                 if (begin < end)
-                    hipLaunchKernelGGL(k_raht_bit<FWD>, dim3(grid_for(end - begin, 256)), dim3(256), 0, s, cross_order, begin, end, n, lo, hi, val, H);
+                    hipLaunchKernelGGL(k_raht_bit<FWD>, dim3(grid_for(end - begin, 256)), dim3(256), 0, s, list, begin, end, n, lo, hi, val, H);
             }
         }
         if (!FWD) hipLaunchKernelGGL(k_raht_store, dim3(grid_for(n, 256)), dim3(256), 0, s, val, perm, n, rgb_out);
@@ -607,17 +506,55 @@ static int raht_run_batch(const uint8_t* rgb_in, uint8_t* rgb_out, const int32_t
             hipLaunchKernelGGL(k_raht_spine<FWD>, dim3(1), dim3(RAHT_SPINE_THREADS), 0, s, cross_order, cross_off_dev, n, lo, hi, val, H);
         if (!FWD) hipLaunchKernelGGL(k_raht_tile<false>, dim3(tiles), dim3(RAHT_THREADS), 0, s, rgb_in, rgb_out, perm, n, d, lo, hi, val, H);
     }
+}
+// what the four entries share; `list`, `off`, `sets` as raht_run takes them; other: the entry's own pointers, all of them non-null
+static int raht_run_args(const char* who, int64_t n, int form, bool other, const void* rgb, const int32_t* perm, const int32_t* val,
+                         const uint8_t* d, const int32_t* lo, const int32_t* hi, const int32_t* list, const int32_t* off, int sets,
+                         const int32_t* cross_order, const int32_t* cross_off, const int32_t* H, const char* unsound) {
+    RAHT_REQUIRE(who, form == 0 || form == 1, "form 0 (one launch per split bit) or 1 (tiles)");
+    RAHT_REQUIRE(who, rgb && perm && val && off && cross_off && other, "null argument");
+    RAHT_REQUIRE(who, n == 1 || (d && lo && hi && list && cross_order && H), "null argument");
+    RAHT_REQUIRE(who, offsets_sound(off, sets, n), unsound);
     return 0;
+}
+static const char* const RAHT_BUCKET_UNSOUND = "bucket offsets are not those of a tree of n leaves";
+static const char* const RAHT_BIT_UNSOUND = "bit offsets are not those of a batch tree of n leaves";
+
+extern "C" int pcgc_raht_forward(const uint8_t* rgb, const int32_t* perm, int64_t n, const uint8_t* d, const int32_t* lo, const int32_t* hi,
+                                 const int32_t* order, const int32_t* bucket_off, const int32_t* cross_order, const int32_t* cross_off, int form,
+                                 int32_t* val, int32_t* H, void* stream) {
+    PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
+    if (int r = raht_run_args(__func__, n, form, true, rgb, perm, val, d, lo, hi, order, bucket_off, 1, cross_order, cross_off, H, RAHT_BUCKET_UNSOUND))
+        return r;
+    raht_run<true>(rgb, nullptr, perm, n, d, lo, hi, order, bucket_off, 1, cross_order, cross_off, form, (i3*)val, (i3*)H, S(stream));
+    PCGC_CHECK_LAUNCH("raht_forward");
+    return 0;
+}
+extern "C" int pcgc_raht_inverse(const int32_t* Hhat, int32_t dc_y, int32_t dc_co, int32_t dc_cg, const int32_t* perm, int64_t n, const uint8_t* d,
+                                 const int32_t* lo, const int32_t* hi, const int32_t* order, const int32_t* bucket_off,
+                                 const int32_t* cross_order, const int32_t* cross_off, int form, int32_t* val, uint8_t* rgb, void* stream) {
+    PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
+    if (int r = raht_run_args(__func__, n, form, true, rgb, perm, val, d, lo, hi, order, bucket_off, 1, cross_order, cross_off, Hhat, RAHT_BUCKET_UNSOUND))
+        return r;
+    hipLaunchKernelGGL(k_raht_set_dc, dim3(1), dim3(64), 0, S(stream), (i3*)val, i3{dc_y, dc_co, dc_cg});
+    raht_run<false>(nullptr, rgb, perm, n, d, lo, hi, order, bucket_off, 1, cross_order, cross_off, form, (i3*)val, (i3*)const_cast<int32_t*>(Hhat),
+                    S(stream));
+    PCGC_CHECK_LAUNCH("raht_inverse");
+    return 0;
+}
+
+// A batch: bit_off [130] on the HOST holds the two groups of 65 offsets into cross_order; every frame's DC stands at the start of its run.
+__global__ void k_raht_set_dc_batch(i3* val, int64_t n, const int32_t* __restrict__ starts, const i3* __restrict__ dc, int frames) {
+    const int b = threadIdx.x;
+    if (b < frames && starts[b] >= 0 && starts[b] < n) val[starts[b]] = dc[b];
 }
 extern "C" int pcgc_raht_forward_batch(const uint8_t* rgb, const int32_t* perm, int64_t n, const uint8_t* d, const int32_t* lo, const int32_t* hi,
                                        const int32_t* cross_order, const int32_t* bit_off, const int32_t* cross_off, int form, int32_t* val,
                                        int32_t* H, void* stream) {
     PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
-    PCGC_REQUIRE(form == 0 || form == 1, "form 0 (one launch per split bit) or 1 (tiles)");
-    PCGC_REQUIRE(rgb && perm && val && bit_off && cross_off, "null argument");
-    PCGC_REQUIRE(n == 1 || (d && lo && hi && cross_order && H), "null argument");
-    PCGC_REQUIRE(bit_offsets_sound(bit_off, n), "bit offsets are not those of a batch tree of n leaves");
-    raht_run_batch<true>(rgb, nullptr, perm, n, d, lo, hi, cross_order, bit_off, cross_off, form, nullptr, nullptr, 0, (i3*)val, (i3*)H, S(stream));
+    if (int r = raht_run_args(__func__, n, form, true, rgb, perm, val, d, lo, hi, cross_order, bit_off, 2, cross_order, cross_off, H, RAHT_BIT_UNSOUND))
+        return r;
+    raht_run<true>(rgb, nullptr, perm, n, d, lo, hi, cross_order, bit_off, 2, cross_order, cross_off, form, (i3*)val, (i3*)H, S(stream));
     PCGC_CHECK_LAUNCH("raht_forward_batch");
     return 0;
 }
@@ -626,15 +563,16 @@ extern "C" int pcgc_raht_inverse_batch(const int32_t* Hhat, const int32_t* dc, c
                                        const int32_t* cross_off, int form, int32_t* val, uint8_t* rgb, void* stream) {
     PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
     PCGC_REQUIRE(frames >= 1 && frames <= RAHT_MAX_FRAMES, "1 to 16 frames");
-    PCGC_REQUIRE(form == 0 || form == 1, "form 0 (one launch per split bit) or 1 (tiles)");
-    PCGC_REQUIRE(rgb && perm && val && bit_off && cross_off && dc && starts, "null argument");
-    PCGC_REQUIRE(n == 1 || (d && lo && hi && cross_order && Hhat), "null argument");
-    PCGC_REQUIRE(bit_offsets_sound(bit_off, n), "bit offsets are not those of a batch tree of n leaves");
-    raht_run_batch<false>(nullptr, rgb, perm, n, d, lo, hi, cross_order, bit_off, cross_off, form, starts, (const i3*)dc, frames, (i3*)val,
-                          (i3*)const_cast<int32_t*>(Hhat), S(stream));
+    if (int r = raht_run_args(__func__, n, form, dc && starts, rgb, perm, val, d, lo, hi, cross_order, bit_off, 2, cross_order, cross_off, Hhat,
+                              RAHT_BIT_UNSOUND))
+        return r;
+    hipLaunchKernelGGL(k_raht_set_dc_batch, dim3(1), dim3(64), 0, S(stream), (i3*)val, n, starts, (const i3*)dc, frames);
+    raht_run<false>(nullptr, rgb, perm, n, d, lo, hi, cross_order, bit_off, 2, cross_order, cross_off, form, (i3*)val,
+                    (i3*)const_cast<int32_t*>(Hhat), S(stream));
     PCGC_CHECK_LAUNCH("raht_inverse_batch");
     return 0;
 }
+
 
 // ------------------------------------------------------------------------------------------------------------------ quantiser
 __device__ static inline uint32_t isqrt64(uint64_t v) {       // v < 2^52
@@ -656,162 +594,46 @@ __device__ static inline int32_t level_z(int32_t H, int64_t D) {               /
     return (int32_t)(z > 63 + 1023 ? 63 + 1023 : z);           // (|H| <= 510 gives z <= 1020; an escape has 10 bits)
 }
 
-// one thread per position of the coding order
-__global__ void __launch_bounds__(256) k_raht_quantize(const i3* __restrict__ H, int64_t gaps, const uint8_t* __restrict__ d8,
-                                                       const int32_t* __restrict__ lo, const int32_t* __restrict__ hi,
-                                                       const int32_t* __restrict__ order, int q_luma, int q_chroma, int16_t* __restrict__ tokens,
-                                                       uint16_t* __restrict__ ctx, uint8_t* __restrict__ escmask, uint16_t* __restrict__ rem,
-                                                       int32_t* hist) {
-    __shared__ int32_t h[RAHT_CONTEXTS * 64];
-    for (int j = threadIdx.x; j < RAHT_CONTEXTS * 64; j += 256) h[j] = 0;
-    __syncthreads();
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < gaps) {
-        const int32_t g = order[p];
-        if (g >= 0 && g < gaps) {
-            const int64_t w1 = g - lo[g] + 1, w2 = hi[g] - g;
-            const i3 v = H[g];
-            const int64_t dl = delta16(q_luma, w1, w2), dc = delta16(q_chroma, w1, w2);
-            const int row = (d8[g] & 63) / 3 < 15 ? (d8[g] & 63) / 3 : 15;
-            const int32_t z[3] = {level_z(v.a, dl), level_z(v.b, dc), level_z(v.c, dc)};
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int t = z[c] < RAHT_ESCAPE ? z[c] : RAHT_ESCAPE;
-                tokens[3 * p + c] = (int16_t)t;
-                ctx[3 * p + c] = (uint16_t)(16 * c + row);
-                escmask[3 * p + c] = t == RAHT_ESCAPE;
-                rem[3 * p + c] = (uint16_t)(t == RAHT_ESCAPE ? z[c] - RAHT_ESCAPE : 0);
-                atomicAdd(&h[(16 * c + row) * 64 + t], 1);
-            }
-        }
-    }
-    __syncthreads();
-    for (int j = threadIdx.x; j < RAHT_CONTEXTS * 64; j += 256) if (h[j]) atomicAdd(hist + j, h[j]);
-}
-__global__ void __launch_bounds__(256) k_raht_compact_esc(const uint8_t* __restrict__ escmask, const int32_t* __restrict__ prefix,
-                                                          const uint16_t* __restrict__ rem, int64_t n, uint16_t* __restrict__ esc) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && escmask[i]) esc[prefix[i]] = rem[i];
-}
-
-static size_t tokens_of(int64_t n) { return (size_t)(n < 2 ? 1 : 3 * (n - 1)); }
-extern "C" size_t pcgc_raht_quantize_workspace_bytes(int64_t n) {
-    const size_t t = tokens_of(n);
-    return align256(t) + align256(t * 2) + align256(t * 4) + align256(pcgc_scan_workspace_bytes((int64_t)t));
-}
-extern "C" int pcgc_raht_quantize(const int32_t* H, int64_t n, const uint8_t* d, const int32_t* lo, const int32_t* hi, const int32_t* order,
-                                  int q_luma, int q_chroma, int16_t* tokens, uint16_t* ctx, uint16_t* escapes, int32_t* n_escapes, int32_t* hist,
-                                  void* workspace, size_t workspace_bytes, void* stream) {
-    PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
-    PCGC_REQUIRE(q_luma >= 0 && q_luma <= 255 && q_chroma >= 0 && q_chroma <= 255, "quantiser 0 .. 255");
-    PCGC_REQUIRE(n_escapes && hist && workspace, "null argument");
-    PCGC_REQUIRE(workspace_bytes >= pcgc_raht_quantize_workspace_bytes(n), "workspace too small");
-    hipError_t e = hipMemsetAsync(hist, 0, RAHT_CONTEXTS * 64 * sizeof(int32_t), S(stream));
-    if (e == hipSuccess) e = hipMemsetAsync(n_escapes, 0, sizeof(int32_t), S(stream));
-    if (e != hipSuccess) { pcgc_set_error("raht_quantize: %s", hipGetErrorString(e)); return -1; }
-    if (n == 1) return 0;
-    PCGC_REQUIRE(H && d && lo && hi && order && tokens && ctx && escapes, "null argument");
-    const int64_t gaps = n - 1, t = 3 * gaps;
-    char* ws = (char*)workspace;
-    uint8_t* escmask = (uint8_t*)ws; ws += align256((size_t)t);
-    uint16_t* rem = (uint16_t*)ws; ws += align256((size_t)t * 2);
-    int32_t* prefix = (int32_t*)ws; ws += align256((size_t)t * 4);
-    hipLaunchKernelGGL(k_raht_quantize, dim3(grid_for(gaps, 256)), dim3(256), 0, S(stream), (const i3*)H, gaps, d, lo, hi, order, q_luma, q_chroma,
-                       tokens, ctx, escmask, rem, hist);
-    PCGC_CHECK_LAUNCH("raht_quantize");
-    if (pcgc_mask_scan(escmask, t, prefix, n_escapes, ws, pcgc_scan_workspace_bytes(t), stream) != 0) return -1;
-    hipLaunchKernelGGL(k_raht_compact_esc, dim3(grid_for(t, 256)), dim3(256), 0, S(stream), escmask, prefix, rem, t, escapes);
-    PCGC_CHECK_LAUNCH("raht_quantize");
-    return 0;
-}
-
-__global__ void __launch_bounds__(256) k_raht_escmask(const int16_t* __restrict__ tokens, int64_t n, uint8_t* __restrict__ escmask) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) escmask[i] = tokens[i] == RAHT_ESCAPE;
-}
-__device__ static inline int32_t dequant(int32_t z, int64_t D) {
-    const int64_t k = z >> 1;                                  // |k| of an even z; an odd z = -2 k - 1 has |k| = (z + 1) / 2
-    const int64_t a = (z & 1) ? k + 1 : k;
-    const int64_t v = (a * D + 8) / 16;
-    return (int32_t)((z & 1) ? -v : v);
-}
-__global__ void __launch_bounds__(256) k_raht_dequantize(const int16_t* __restrict__ tokens, const int32_t* __restrict__ prefix,
-                                                         const uint16_t* __restrict__ esc, int64_t n_esc, int64_t gaps,
-                                                         const int32_t* __restrict__ lo, const int32_t* __restrict__ hi,
-                                                         const int32_t* __restrict__ order, int q_luma, int q_chroma, i3* __restrict__ Hhat) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= gaps) return;
-    const int32_t g = order[p];
-    if (g < 0 || g >= gaps) return;
-    const int64_t w1 = g - lo[g] + 1, w2 = hi[g] - g;
-    int32_t z[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        int32_t t = tokens[3 * p + c];
-        t = t < 0 ? 0 : (t > RAHT_ESCAPE ? RAHT_ESCAPE : t);
-        if (t == RAHT_ESCAPE) { const int64_t e = prefix[3 * p + c]; t += e < n_esc ? (esc[e] & 1023) : 0; }
-        z[c] = t;
-    }
-    const int64_t dl = delta16(q_luma, w1, w2), dc = delta16(q_chroma, w1, w2);
-    Hhat[g] = i3{dequant(z[0], dl), dequant(z[1], dc), dequant(z[2], dc)};
-}
-extern "C" size_t pcgc_raht_dequantize_workspace_bytes(int64_t n) {
-    const size_t t = tokens_of(n);
-    return align256(t) + align256(t * 4) + align256(pcgc_scan_workspace_bytes((int64_t)t));
-}
-// n_escape_tokens: the number of tokens equal to 63; the caller refuses a stream whose escape list has another length
-extern "C" int pcgc_raht_dequantize(const int16_t* tokens, const uint16_t* escapes, int64_t n_escapes, int64_t n, const int32_t* lo, const int32_t* hi,
-                                    const int32_t* order, int q_luma, int q_chroma, int32_t* Hhat, int32_t* n_escape_tokens, void* workspace,
-                                    size_t workspace_bytes, void* stream) {
-    PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
-    PCGC_REQUIRE(q_luma >= 0 && q_luma <= 255 && q_chroma >= 0 && q_chroma <= 255, "quantiser 0 .. 255");
-    PCGC_REQUIRE(n_escapes >= 0 && n_escape_tokens && workspace, "bad argument");
-    PCGC_REQUIRE(workspace_bytes >= pcgc_raht_dequantize_workspace_bytes(n), "workspace too small");
-    if (n == 1) { (void)hipMemsetAsync(n_escape_tokens, 0, sizeof(int32_t), S(stream)); return 0; }
-    PCGC_REQUIRE(tokens && lo && hi && order && Hhat && (n_escapes == 0 || escapes), "null argument");
-    const int64_t gaps = n - 1, t = 3 * gaps;
-    char* ws = (char*)workspace;
-    uint8_t* escmask = (uint8_t*)ws; ws += align256((size_t)t);
-    int32_t* prefix = (int32_t*)ws; ws += align256((size_t)t * 4);
-    hipLaunchKernelGGL(k_raht_escmask, dim3(grid_for(t, 256)), dim3(256), 0, S(stream), tokens, t, escmask);
-    PCGC_CHECK_LAUNCH("raht_dequantize");
-    if (pcgc_mask_scan(escmask, t, prefix, n_escape_tokens, ws, pcgc_scan_workspace_bytes(t), stream) != 0) return -1;
-    hipLaunchKernelGGL(k_raht_dequantize, dim3(grid_for(gaps, 256)), dim3(256), 0, S(stream), tokens, prefix, escapes, n_escapes, gaps, lo, hi, order,
-                       q_luma, q_chroma, (i3*)Hhat);
-    PCGC_CHECK_LAUNCH("raht_dequantize");
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------------------------ quantiser, a batch
-// coded = n - frames positions of the batch's coding order (the frame boundaries lie behind them); the frame of a position is bits 60 .. 63
-// of its gap's key, its steps come from a table passed by value
+// The steps of every frame, passed by value.  coded = n - frames positions of the coding order (a batch's frame boundaries lie behind them).
+// The frame of a position is bits 60 .. 63 of its gap's key; with one frame it is 0 and `keys` is not read (the single entries pass null).
 struct RahtSteps { uint8_t luma[RAHT_MAX_FRAMES], chroma[RAHT_MAX_FRAMES]; };
 
-__global__ void __launch_bounds__(256) k_raht_quantize_batch(const i3* __restrict__ H, int64_t coded, int64_t gaps, const uint64_t* __restrict__ keys,
-                                                             const uint8_t* __restrict__ d8, const int32_t* __restrict__ lo,
-                                                             const int32_t* __restrict__ hi, const int32_t* __restrict__ order, RahtSteps q,
-                                                             int16_t* __restrict__ tokens, uint16_t* __restrict__ ctx, uint8_t* __restrict__ escmask,
-                                                             uint16_t* __restrict__ rem, int32_t* hist) {
+// the frame of gap g, -1 for a gap that is no merge of frames 0 .. frames - 1 (never, for a tree pcgc_raht_tree built)
+__device__ static inline int frame_of_gap(const uint64_t* __restrict__ keys, int frames, int64_t gaps, int32_t g, const int32_t* __restrict__ lo) {
+    if (g < 0 || g >= gaps || lo[g] < 0) return -1;
+    const int f = frames > 1 ? (int)(keys[g] >> RAHT_FRAME_BIT) : 0;
+    return f < frames ? f : -1;
+}
+// frame f's steps.  A lane's own index into the by-value table is a load from the kernel's arguments in memory; a single frame reads
+// entry 0, which is a scalar register like the two ints it stands for
+__device__ static inline void steps_at(const RahtSteps& q, int frames, int f, int& q_luma, int& q_chroma) {
+    q_luma = frames > 1 ? q.luma[f] : q.luma[0];
+    q_chroma = frames > 1 ? q.chroma[f] : q.chroma[0];
+}
+// one thread per position of the coding order; hist [frames, 48, 64]
+__global__ void __launch_bounds__(256) k_raht_quantize(const i3* __restrict__ H, int64_t coded, int64_t gaps, int frames, const uint64_t* __restrict__ keys,
+                                                       const uint8_t* __restrict__ d8, const int32_t* __restrict__ lo, const int32_t* __restrict__ hi,
+                                                       const int32_t* __restrict__ order, RahtSteps q, int16_t* __restrict__ tokens,
+                                                       uint16_t* __restrict__ ctx, uint8_t* __restrict__ escmask, uint16_t* __restrict__ rem,
+                                                       int32_t* hist) {
     // the block's LDS histogram is that of the frame of its first position; the few positions of a block that belong to a later frame go
     // to the global histogram directly (integer atomics either way: the sums do not depend on the order)
     __shared__ int32_t h[RAHT_CONTEXTS * 64];
     __shared__ int f0_s;
     for (int j = threadIdx.x; j < RAHT_CONTEXTS * 64; j += 256) h[j] = 0;
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int32_t g = -1;
-    int f = -1;
-    if (p < coded) {
-        g = order[p];
-        if (g >= 0 && g < gaps && d8[g] < RAHT_FRAME_BIT && lo[g] >= 0) f = (int)(keys[g] >> RAHT_FRAME_BIT); else g = -1;
-    }
+    const int32_t g = p < coded ? order[p] : -1;
+    const int f = frame_of_gap(keys, frames, gaps, g, lo);
     if (threadIdx.x == 0) f0_s = f;
     __syncthreads();
     const int f0 = f0_s;
-    if (g >= 0) {
+    if (f >= 0) {
         const int64_t w1 = g - lo[g] + 1, w2 = hi[g] - g;
         const i3 v = H[g];
-        const int64_t dl = delta16(q.luma[f], w1, w2), dc = delta16(q.chroma[f], w1, w2);
-        const int row = d8[g] / 3 < 15 ? d8[g] / 3 : 15;
+        int q_luma, q_chroma;
+        steps_at(q, frames, f, q_luma, q_chroma);
+        const int64_t dl = delta16(q_luma, w1, w2), dc = delta16(q_chroma, w1, w2);
+        const int row = (d8[g] & 63) / 3 < 15 ? (d8[g] & 63) / 3 : 15;
         const int32_t z[3] = {level_z(v.a, dl), level_z(v.b, dc), level_z(v.c, dc)};
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -823,13 +645,18 @@ __global__ void __launch_bounds__(256) k_raht_quantize_batch(const i3* __restric
             if (f == f0) atomicAdd(&h[(16 * c + row) * 64 + t], 1);
             else atomicAdd(hist + ((int64_t)f * RAHT_CONTEXTS + 16 * c + row) * 64 + t, 1);
         }
-    } else if (p < coded) {                                    // (never, for a tree pcgc_raht_tree_batch built)
+    } else if (p < coded) {                                    // (never, see frame_of_gap)
 #pragma unroll
         for (int c = 0; c < 3; ++c) { tokens[3 * p + c] = 0; ctx[3 * p + c] = (uint16_t)(16 * c); escmask[3 * p + c] = 0; rem[3 * p + c] = 0; }
     }
     __syncthreads();
     if (f0 >= 0)
         for (int j = threadIdx.x; j < RAHT_CONTEXTS * 64; j += 256) if (h[j]) atomicAdd(hist + (int64_t)f0 * RAHT_CONTEXTS * 64 + j, h[j]);
+}
+__global__ void __launch_bounds__(256) k_raht_compact_esc(const uint8_t* __restrict__ escmask, const int32_t* __restrict__ prefix,
+                                                          const uint16_t* __restrict__ rem, int64_t n, uint16_t* __restrict__ esc) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && escmask[i]) esc[prefix[i]] = rem[i];
 }
 
 static bool steps_of(const int32_t* q_luma, const int32_t* q_chroma, int frames, RahtSteps& q) {
@@ -840,67 +667,94 @@ static bool steps_of(const int32_t* q_luma, const int32_t* q_chroma, int frames,
     }
     return true;
 }
-static size_t tokens_of_batch(int64_t n, int frames) { return (size_t)(n - frames < 1 ? 1 : 3 * (n - frames)); }
+static size_t tokens_of(int64_t n, int frames) { return (size_t)(n - frames < 1 ? 1 : 3 * (n - frames)); }
 
-extern "C" int64_t pcgc_raht_quantize_batch_workspace_bytes(int64_t n, int frames) {
-    const size_t t = tokens_of_batch(n, frames);
-    return (int64_t)(align256(t) + align256(t * 2) + align256(t * 4) + align256(pcgc_scan_workspace_bytes((int64_t)t)));
+static size_t quantize_workspace_bytes(int64_t n, int frames) {
+    const size_t t = tokens_of(n, frames);
+    return align256(t) + align256(t * 2) + align256(t * 4) + align256(pcgc_scan_workspace_bytes((int64_t)t));
 }
+static int raht_quantize(const char* who, const int32_t* H, int64_t n, int frames, const uint64_t* keys, const uint8_t* d, const int32_t* lo,
+                         const int32_t* hi, const int32_t* order, const RahtSteps& q, int16_t* tokens, uint16_t* ctx, uint16_t* escapes,
+                         int32_t* n_escapes, int32_t* hist, void* workspace, size_t workspace_bytes, void* stream) {
+    RAHT_REQUIRE(who, n_escapes && hist && workspace, "null argument");
+    RAHT_REQUIRE(who, workspace_bytes >= quantize_workspace_bytes(n, frames), "workspace too small");
+    hipError_t e = hipMemsetAsync(hist, 0, (size_t)frames * RAHT_CONTEXTS * 64 * sizeof(int32_t), S(stream));
+    if (e == hipSuccess) e = hipMemsetAsync(n_escapes, 0, sizeof(int32_t), S(stream));
+    RAHT_CHECK_HIP(who, e);
+    if (n == frames) return 0;
+    RAHT_REQUIRE(who, H && (frames == 1 || keys) && d && lo && hi && order && tokens && ctx && escapes, "null argument");
+    const int64_t coded = n - frames, t = 3 * coded;
+    char* ws = (char*)workspace;
+    uint8_t* escmask = (uint8_t*)ws; ws += align256((size_t)t);
+    uint16_t* rem = (uint16_t*)ws; ws += align256((size_t)t * 2);
+    int32_t* prefix = (int32_t*)ws; ws += align256((size_t)t * 4);
+    hipLaunchKernelGGL(k_raht_quantize, dim3(grid_for(coded, 256)), dim3(256), 0, S(stream), (const i3*)H, coded, n - 1, frames, keys, d, lo, hi, order,
+                       q, tokens, ctx, escmask, rem, hist);
+    PCGC_CHECK_LAUNCH(who + 5);
+    if (pcgc_mask_scan(escmask, t, prefix, n_escapes, ws, pcgc_scan_workspace_bytes(t), stream) != 0) return -1;
+    hipLaunchKernelGGL(k_raht_compact_esc, dim3(grid_for(t, 256)), dim3(256), 0, S(stream), escmask, prefix, rem, t, escapes);
+    PCGC_CHECK_LAUNCH(who + 5);
+    return 0;
+}
+extern "C" size_t pcgc_raht_quantize_workspace_bytes(int64_t n) { return quantize_workspace_bytes(n, 1); }
+extern "C" int pcgc_raht_quantize(const int32_t* H, int64_t n, const uint8_t* d, const int32_t* lo, const int32_t* hi, const int32_t* order,
+                                  int q_luma, int q_chroma, int16_t* tokens, uint16_t* ctx, uint16_t* escapes, int32_t* n_escapes, int32_t* hist,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
+    RahtSteps q;
+    PCGC_REQUIRE(steps_of(&q_luma, &q_chroma, 1, q), "quantiser 0 .. 255");
+    return raht_quantize(__func__, H, n, 1, nullptr, d, lo, hi, order, q, tokens, ctx, escapes, n_escapes, hist, workspace, workspace_bytes, stream);
+}
+extern "C" int64_t pcgc_raht_quantize_batch_workspace_bytes(int64_t n, int frames) { return (int64_t)quantize_workspace_bytes(n, frames); }
 extern "C" int pcgc_raht_quantize_batch(const int32_t* H, int64_t n, int frames, const uint64_t* keys, const uint8_t* d, const int32_t* lo,
                                         const int32_t* hi, const int32_t* order, const int32_t* q_luma, const int32_t* q_chroma, int16_t* tokens,
                                         uint16_t* ctx, uint16_t* escapes, int32_t* n_escapes, int32_t* hist, void* workspace,
                                         size_t workspace_bytes, void* stream) {
     PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
     PCGC_REQUIRE(frames >= 1 && frames <= RAHT_MAX_FRAMES && frames <= n, "1 to 16 frames of at least one point");
-    PCGC_REQUIRE(q_luma && q_chroma && n_escapes && hist && workspace, "null argument");
+    PCGC_REQUIRE(q_luma && q_chroma, "null argument");
     RahtSteps q;
     PCGC_REQUIRE(steps_of(q_luma, q_chroma, frames, q), "quantiser 0 .. 255");
-    PCGC_REQUIRE(workspace_bytes >= (size_t)pcgc_raht_quantize_batch_workspace_bytes(n, frames), "workspace too small");
-    hipError_t e = hipMemsetAsync(hist, 0, (size_t)frames * RAHT_CONTEXTS * 64 * sizeof(int32_t), S(stream));
-    if (e == hipSuccess) e = hipMemsetAsync(n_escapes, 0, sizeof(int32_t), S(stream));
-    if (e != hipSuccess) { pcgc_set_error("raht_quantize_batch: %s", hipGetErrorString(e)); return -1; }
-    if (n == frames) return 0;
-    PCGC_REQUIRE(H && keys && d && lo && hi && order && tokens && ctx && escapes, "null argument");
-    const int64_t coded = n - frames, t = 3 * coded;
-    char* ws = (char*)workspace;
-    uint8_t* escmask = (uint8_t*)ws; ws += align256((size_t)t);
-    uint16_t* rem = (uint16_t*)ws; ws += align256((size_t)t * 2);
-    int32_t* prefix = (int32_t*)ws; ws += align256((size_t)t * 4);
-    hipLaunchKernelGGL(k_raht_quantize_batch, dim3(grid_for(coded, 256)), dim3(256), 0, S(stream), (const i3*)H, coded, n - 1, keys, d, lo, hi, order,
-                       q, tokens, ctx, escmask, rem, hist);
-    PCGC_CHECK_LAUNCH("raht_quantize_batch");
-    if (pcgc_mask_scan(escmask, t, prefix, n_escapes, ws, pcgc_scan_workspace_bytes(t), stream) != 0) return -1;
-    hipLaunchKernelGGL(k_raht_compact_esc, dim3(grid_for(t, 256)), dim3(256), 0, S(stream), escmask, prefix, rem, t, escapes);
-    PCGC_CHECK_LAUNCH("raht_quantize_batch");
-    return 0;
+    return raht_quantize(__func__, H, n, frames, keys, d, lo, hi, order, q, tokens, ctx, escapes, n_escapes, hist, workspace, workspace_bytes, stream);
 }
 
-// the mask of the tokens that are 63, and how many of them each frame has (counts [16], zeroed by the caller)
-__global__ void __launch_bounds__(256) k_raht_escmask_batch(const int16_t* __restrict__ tokens, int64_t n, const int32_t* __restrict__ order,
-                                                            const uint64_t* __restrict__ keys, int64_t gaps, uint8_t* __restrict__ escmask,
-                                                            int32_t* counts) {
+// ------------------------------------------------------------------------------------------------------------------ dequantiser
+// the mask of the tokens that are 63, and how many of them each frame has (counts [16], zeroed by the caller; null: nobody asks)
+__global__ void __launch_bounds__(256) k_raht_escmask(const int16_t* __restrict__ tokens, int64_t n, const int32_t* __restrict__ order,
+                                                      const uint64_t* __restrict__ keys, const int32_t* __restrict__ lo, int64_t gaps, int frames,
+                                                      uint8_t* __restrict__ escmask, int32_t* counts) {
     __shared__ int32_t c[RAHT_MAX_FRAMES];
-    if (threadIdx.x < RAHT_MAX_FRAMES) c[threadIdx.x] = 0;
-    __syncthreads();
+    if (counts) {                                              // (uniform)
+        if (threadIdx.x < RAHT_MAX_FRAMES) c[threadIdx.x] = 0;
+        __syncthreads();
+    }
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
         const bool m = tokens[i] == RAHT_ESCAPE;
         escmask[i] = m;
-        if (m) { const int32_t g = order[i / 3]; if (g >= 0 && g < gaps) atomicAdd(&c[(int)(keys[g] >> RAHT_FRAME_BIT)], 1); }
+        if (m && counts) { const int f = frame_of_gap(keys, frames, gaps, order[i / 3], lo); if (f >= 0) atomicAdd(&c[f], 1); }
     }
-    __syncthreads();
-    if (threadIdx.x < RAHT_MAX_FRAMES && c[threadIdx.x]) atomicAdd(counts + threadIdx.x, c[threadIdx.x]);
+    if (counts) {
+        __syncthreads();
+        if (threadIdx.x < RAHT_MAX_FRAMES && c[threadIdx.x]) atomicAdd(counts + threadIdx.x, c[threadIdx.x]);
+    }
 }
-__global__ void __launch_bounds__(256) k_raht_dequantize_batch(const int16_t* __restrict__ tokens, const int32_t* __restrict__ prefix,
-                                                               const uint16_t* __restrict__ esc, int64_t n_esc, int64_t coded, int64_t gaps,
-                                                               const uint64_t* __restrict__ keys, const int32_t* __restrict__ lo,
-                                                               const int32_t* __restrict__ hi, const int32_t* __restrict__ order, RahtSteps q,
-                                                               i3* __restrict__ Hhat) {
+__device__ static inline int32_t dequant(int32_t z, int64_t D) {
+    const int64_t k = z >> 1;                                  // |k| of an even z; an odd z = -2 k - 1 has |k| = (z + 1) / 2
+    const int64_t a = (z & 1) ? k + 1 : k;
+    const int64_t v = (a * D + 8) / 16;
+    return (int32_t)((z & 1) ? -v : v);
+}
+__global__ void __launch_bounds__(256) k_raht_dequantize(const int16_t* __restrict__ tokens, const int32_t* __restrict__ prefix,
+                                                         const uint16_t* __restrict__ esc, int64_t n_esc, int64_t coded, int64_t gaps, int frames,
+                                                         const uint64_t* __restrict__ keys, const int32_t* __restrict__ lo,
+                                                         const int32_t* __restrict__ hi, const int32_t* __restrict__ order, RahtSteps q,
+                                                         i3* __restrict__ Hhat) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= coded) return;
     const int32_t g = order[p];
-    if (g < 0 || g >= gaps || lo[g] < 0) return;
-    const int f = (int)(keys[g] >> RAHT_FRAME_BIT);
+    const int f = frame_of_gap(keys, frames, gaps, g, lo);
+    if (f < 0) return;
     const int64_t w1 = g - lo[g] + 1, w2 = hi[g] - g;
     int32_t z[3];
 #pragma unroll
@@ -910,36 +764,62 @@ __global__ void __launch_bounds__(256) k_raht_dequantize_batch(const int16_t* __
         if (t == RAHT_ESCAPE) { const int64_t e = prefix[3 * p + c]; t += e < n_esc ? (esc[e] & 1023) : 0; }
         z[c] = t;
     }
-    const int64_t dl = delta16(q.luma[f], w1, w2), dc = delta16(q.chroma[f], w1, w2);
+    int q_luma, q_chroma;
+    steps_at(q, frames, f, q_luma, q_chroma);
+    const int64_t dl = delta16(q_luma, w1, w2), dc = delta16(q_chroma, w1, w2);
     Hhat[g] = i3{dequant(z[0], dl), dequant(z[1], dc), dequant(z[2], dc)};
 }
-extern "C" int64_t pcgc_raht_dequantize_batch_workspace_bytes(int64_t n, int frames) {
-    const size_t t = tokens_of_batch(n, frames);
-    return (int64_t)(align256(t) + align256(t * 4) + align256(pcgc_scan_workspace_bytes((int64_t)t)));
+
+static size_t dequantize_workspace_bytes(int64_t n, int frames) {
+    const size_t t = tokens_of(n, frames);
+    return align256(t) + align256(t * 4) + align256(pcgc_scan_workspace_bytes((int64_t)t));
 }
+// per_frame [16] (dev, null for a single frame) and total [1] (dev): the tokens equal to 63; the caller refuses a stream whose escape lists
+// have other lengths
+static int raht_dequantize(const char* who, const int16_t* tokens, const uint16_t* escapes, int64_t n_escapes, int64_t n, int frames,
+                           const uint64_t* keys, const int32_t* lo, const int32_t* hi, const int32_t* order, const RahtSteps& q, int32_t* Hhat,
+                           int32_t* per_frame, int32_t* total, void* workspace, size_t workspace_bytes, void* stream) {
+    RAHT_REQUIRE(who, n_escapes >= 0 && total && workspace, "bad argument");
+    RAHT_REQUIRE(who, workspace_bytes >= dequantize_workspace_bytes(n, frames), "workspace too small");
+    hipError_t e = per_frame ? hipMemsetAsync(per_frame, 0, RAHT_MAX_FRAMES * sizeof(int32_t), S(stream)) : hipSuccess;
+    if (e == hipSuccess && n == frames) e = hipMemsetAsync(total, 0, sizeof(int32_t), S(stream));      // (else pcgc_mask_scan writes it)
+    RAHT_CHECK_HIP(who, e);
+    if (n == frames) return 0;
+    RAHT_REQUIRE(who, tokens && (frames == 1 || keys) && lo && hi && order && Hhat && (n_escapes == 0 || escapes), "null argument");
+    const int64_t coded = n - frames, t = 3 * coded;
+    char* ws = (char*)workspace;
+    uint8_t* escmask = (uint8_t*)ws; ws += align256((size_t)t);
+    int32_t* prefix = (int32_t*)ws; ws += align256((size_t)t * 4);
+    hipLaunchKernelGGL(k_raht_escmask, dim3(grid_for(t, 256)), dim3(256), 0, S(stream), tokens, t, order, keys, lo, n - 1, frames, escmask, per_frame);
+    PCGC_CHECK_LAUNCH(who + 5);
+    if (pcgc_mask_scan(escmask, t, prefix, total, ws, pcgc_scan_workspace_bytes(t), stream) != 0) return -1;
+    hipLaunchKernelGGL(k_raht_dequantize, dim3(grid_for(coded, 256)), dim3(256), 0, S(stream), tokens, (const int32_t*)prefix, escapes, n_escapes, coded,
+                       n - 1, frames, keys, lo, hi, order, q, (i3*)Hhat);
+    PCGC_CHECK_LAUNCH(who + 5);
+    return 0;
+}
+extern "C" size_t pcgc_raht_dequantize_workspace_bytes(int64_t n) { return dequantize_workspace_bytes(n, 1); }
+extern "C" int pcgc_raht_dequantize(const int16_t* tokens, const uint16_t* escapes, int64_t n_escapes, int64_t n, const int32_t* lo, const int32_t* hi,
+                                    const int32_t* order, int q_luma, int q_chroma, int32_t* Hhat, int32_t* n_escape_tokens, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
+    RahtSteps q;
+    PCGC_REQUIRE(steps_of(&q_luma, &q_chroma, 1, q), "quantiser 0 .. 255");
+    return raht_dequantize(__func__, tokens, escapes, n_escapes, n, 1, nullptr, lo, hi, order, q, Hhat, nullptr, n_escape_tokens, workspace,
+                           workspace_bytes, stream);
+}
+// n_escape_tokens [17] (dev): the tokens that are 63 per frame, then [16] of all frames
+extern "C" int64_t pcgc_raht_dequantize_batch_workspace_bytes(int64_t n, int frames) { return (int64_t)dequantize_workspace_bytes(n, frames); }
 extern "C" int pcgc_raht_dequantize_batch(const int16_t* tokens, const uint16_t* escapes, int64_t n_escapes, int64_t n, int frames,
                                           const uint64_t* keys, const int32_t* lo, const int32_t* hi, const int32_t* order, const int32_t* q_luma,
                                           const int32_t* q_chroma, int32_t* Hhat, int32_t* n_escape_tokens, void* workspace,
                                           size_t workspace_bytes, void* stream) {
     PCGC_REQUIRE(n >= 1 && n <= RAHT_MAX_POINTS, "1 to 2^24 points");
     PCGC_REQUIRE(frames >= 1 && frames <= RAHT_MAX_FRAMES && frames <= n, "1 to 16 frames of at least one point");
-    PCGC_REQUIRE(q_luma && q_chroma && n_escapes >= 0 && n_escape_tokens && workspace, "bad argument");
+    PCGC_REQUIRE(q_luma && q_chroma && n_escape_tokens, "bad argument");
     RahtSteps q;
     PCGC_REQUIRE(steps_of(q_luma, q_chroma, frames, q), "quantiser 0 .. 255");
-    PCGC_REQUIRE(workspace_bytes >= (size_t)pcgc_raht_dequantize_batch_workspace_bytes(n, frames), "workspace too small");
-    hipError_t e = hipMemsetAsync(n_escape_tokens, 0, (RAHT_MAX_FRAMES + 1) * sizeof(int32_t), S(stream));
-    if (e != hipSuccess) { pcgc_set_error("raht_dequantize_batch: %s", hipGetErrorString(e)); return -1; }
-    if (n == frames) return 0;
-    PCGC_REQUIRE(tokens && keys && lo && hi && order && Hhat && (n_escapes == 0 || escapes), "null argument");
-    const int64_t coded = n - frames, t = 3 * coded;
-    char* ws = (char*)workspace;
-    uint8_t* escmask = (uint8_t*)ws; ws += align256((size_t)t);
-    int32_t* prefix = (int32_t*)ws; ws += align256((size_t)t * 4);
-    hipLaunchKernelGGL(k_raht_escmask_batch, dim3(grid_for(t, 256)), dim3(256), 0, S(stream), tokens, t, order, keys, n - 1, escmask, n_escape_tokens);
-    PCGC_CHECK_LAUNCH("raht_dequantize_batch");
-    if (pcgc_mask_scan(escmask, t, prefix, n_escape_tokens + RAHT_MAX_FRAMES, ws, pcgc_scan_workspace_bytes(t), stream) != 0) return -1;
-    hipLaunchKernelGGL(k_raht_dequantize_batch, dim3(grid_for(coded, 256)), dim3(256), 0, S(stream), tokens, prefix, escapes, n_escapes, coded, n - 1,
-                       keys, lo, hi, order, q, (i3*)Hhat);
-    PCGC_CHECK_LAUNCH("raht_dequantize_batch");
-    return 0;
+    return raht_dequantize(__func__, tokens, escapes, n_escapes, n, frames, keys, lo, hi, order, q, Hhat, n_escape_tokens,
+                           n_escape_tokens + RAHT_MAX_FRAMES, workspace, workspace_bytes, stream);
 }
+

@@ -1664,11 +1664,31 @@ class RahtTree:
         return self.hi - torch.arange(self.n - 1, dtype=torch.int32, device=self.device)
 
 
+def tick_phase(times, phase, t0, dev=None):
+    """The measurement hook of the colour codec (raht_tree, raht_tree_batch, attributes.AttributeCoder).  times None: nothing happens.
+    Else: dev is synchronised (when given) and the seconds since t0 are added to times[phase] (when phase is given) -> now"""
+    import time
+    if times is None:
+        return 0.0
+    if dev is not None:
+        torch.cuda.synchronize(dev)
+    now = time.perf_counter()
+    if phase is not None:
+        times[phase] = times.get(phase, 0.0) + now - t0
+    return now
+
+
+def _raht_gap_arrays(t, n, dev):
+    """the seven per-gap arrays of a tree of n leaves: d uint8 and lo, hi, left, right, order, cross_order int32, each [n - 1]"""
+    g = max(n - 1, 1)
+    t.d = torch.empty(g, dtype=torch.uint8, device=dev)[:n - 1]
+    t.lo, t.hi, t.left, t.right, t.order, t.cross_order = (torch.empty(g, dtype=torch.int32, device=dev)[:n - 1] for _ in range(6))
+
+
 def raht_tree(coords, times=None):
     """coords int32 [n,4] (batch 0, x, y, z in [0, 2^20)) of ONE frame of distinct voxels -> RahtTree.  ValueError for a batch, coordinates
     out of range, duplicates, an empty cloud or more than 2^24 rows.  times (measurement hook): a dict -> seconds of 'keys + sort' and
     'tree' added to it, with a synchronisation after each."""
-    import time
     coords = _i32(coords)
     if coords.dim() != 2 or coords.shape[1] != 4:
         raise ValueError(f'raht_tree: coordinates must be [n,4], got {tuple(coords.shape)}')
@@ -1677,28 +1697,16 @@ def raht_tree(coords, times=None):
         raise ValueError(f'raht_tree: {n} rows; the colour transform takes 1 .. 2^24')
     t = RahtTree()
     t.n, t.device = n, dev
-    g = max(n - 1, 1)
     t.keys = torch.empty(n, dtype=torch.int64, device=dev)
     t.perm = torch.empty(n, dtype=torch.int32, device=dev)
     status = torch.empty(2, dtype=torch.int32, device=dev)
     ws_bytes = max(int(lib().pcgc_raht_keys_workspace_bytes(n)), int(lib().pcgc_raht_tree_workspace_bytes(n)))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     s = _stream(coords)
-
-    def tick(phase, t0):
-        if times is None:
-            return 0.0
-        torch.cuda.synchronize(dev)
-        now = time.perf_counter()
-        if phase is not None:
-            times[phase] = times.get(phase, 0.0) + now - t0
-        return now
-
-    t0 = tick(None, 0.0)
+    t0 = tick_phase(times, None, 0.0, dev)
     check(lib().pcgc_raht_keys(_p(coords), n, _p(t.keys), _p(t.perm), _p(status), _p(ws), ws_bytes, s), 'raht_keys')
-    t0 = tick('keys + sort', t0)
-    t.d =torch.empty(g, dtype=torch.uint8, device=dev)[:n - 1]
-    t.lo, t.hi, t.left, t.right, t.order, t.cross_order = (torch.empty(g, dtype=torch.int32, device=dev)[:n - 1] for _ in range(6))
+    t0 = tick_phase(times, 'keys + sort', t0, dev)
+    _raht_gap_arrays(t, n, dev)
     t.offsets = torch.empty(130, dtype=torch.int32, device=dev)
     check(lib().pcgc_raht_tree(_p(t.keys), n, _p(t.d), _p(t.lo), _p(t.hi), _p(t.left), _p(t.right), _p(t.order), _p(t.cross_order),
                                _p(t.offsets), _p(ws), ws_bytes, s), 'raht_tree')
@@ -1710,8 +1718,8 @@ def raht_tree(coords, times=None):
     if dups:
         raise ValueError(f'raht_tree: {dups} duplicate voxels; the colour transform needs distinct voxels')
     off = t.offsets.cpu().numpy()
-    tick('tree', t0)
-    t.bucket, t.cross =np.ascontiguousarray(off[:65]), np.ascontiguousarray(off[65:])
+    tick_phase(times, 'tree', t0, dev)
+    t.bucket, t.cross = np.ascontiguousarray(off[:65]), np.ascontiguousarray(off[65:])
     return t
 
 
@@ -1806,7 +1814,6 @@ def raht_tree_batch(coords, frames, times=None):
     """coords int32 [n,4] rows (b, x, y, z), b in 0 .. frames - 1 and x, y, z in [0, 2^20), in any order -> RahtBatchTree.  ValueError for
     frames outside 1 .. 16, a frame index outside 0 .. frames - 1 or without rows, coordinates out of range, duplicates within a frame (the
     frame is named), an empty batch or more than 2^24 rows."""
-    import time
     coords = _i32(coords)
     if coords.dim() != 2 or coords.shape[1] != 4:
         raise ValueError(f'raht_tree_batch: coordinates must be [n,4], got {tuple(coords.shape)}')
@@ -1817,28 +1824,16 @@ def raht_tree_batch(coords, frames, times=None):
         raise ValueError(f'raht_tree_batch: {n} rows; the colour transform takes 1 .. 2^24 in a batch')
     t = RahtBatchTree()
     t.n, t.device, t.frames = n, dev, B
-    g = max(n - 1, 1)
     t.keys = torch.empty(n, dtype=torch.int64, device=dev)
     t.perm = torch.empty(n, dtype=torch.int32, device=dev)
     status = torch.empty(34, dtype=torch.int32, device=dev)
     ws_bytes = max(int(lib().pcgc_raht_keys_batch_workspace_bytes(n)), int(lib().pcgc_raht_tree_batch_workspace_bytes(n)))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     s = _stream(coords)
-
-    def tick(phase, t0):
-        if times is None:
-            return 0.0
-        torch.cuda.synchronize(dev)
-        now = time.perf_counter()
-        if phase is not None:
-            times[phase] = times.get(phase, 0.0) + now - t0
-        return now
-
-    t0 = tick(None, 0.0)
+    t0 = tick_phase(times, None, 0.0, dev)
     check(lib().pcgc_raht_keys_batch(_p(coords), n, B, _p(t.keys), _p(t.perm), _p(status), _p(ws), ws_bytes, s), 'raht_keys_batch')
-    t0 = tick('keys + sort', t0)
-    t.d = torch.empty(g, dtype=torch.uint8, device=dev)[:n - 1]
-    t.lo, t.hi, t.left, t.right, t.order, t.cross_order = (torch.empty(g, dtype=torch.int32, device=dev)[:n - 1] for _ in range(6))
+    t0 = tick_phase(times, 'keys + sort', t0, dev)
+    _raht_gap_arrays(t, n, dev)
     t.offsets = torch.empty((B + 1) * 65, dtype=torch.int32, device=dev)
     check(lib().pcgc_raht_tree_batch(_p(t.keys), n, B, _p(t.d), _p(t.lo), _p(t.hi), _p(t.left), _p(t.right), _p(t.order), _p(t.cross_order),
                                      _p(t.offsets), _p(ws), ws_bytes, s), 'raht_tree_batch')
@@ -1854,7 +1849,7 @@ def raht_tree_batch(coords, frames, times=None):
         b = int(np.flatnonzero(dups)[0])
         raise ValueError(f'raht_tree_batch: frame {b} has {int(dups[b])} duplicate voxels; the colour transform needs distinct voxels')
     off = t.offsets.cpu().numpy().reshape(B + 1, 65)
-    tick('tree', t0)
+    tick_phase(times, 'tree', t0, dev)
     t.bucket, t.cross = np.ascontiguousarray(off[:B]), np.ascontiguousarray(off[B])
     t.starts = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
     t.starts_dev = torch.from_numpy(t.starts[:B].astype(np.int32)).to(dev)

@@ -258,6 +258,65 @@ def test_rows_in_any_order_and_repeatability(tmp_path):
     assert _check(tmp_path, frames, ql=3, qc=6, tag='o3') == first                # two runs, the same bytes
 
 
+# ---- a single frame is the batch of one --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('n', [1, 2, 3, T - 1, T, T + 1, 2 * T + 1])
+def test_single_entries_are_the_batch_of_one(n):
+    """every array the single entries give against the batch entries' at B = 1, below the level of a whole file"""
+    pts = AT._random_cloud(n, 64, n)
+    coords, rgb = AT._coords(pts), torch.from_numpy(AT._colours('random', pts, n)).to(DEV)      # (random colours: Q = 0 escapes)
+    one, bat = ops.raht_tree(coords), ops.raht_tree_batch(coords, 1)
+    assert one.n == bat.n == n and bat.frames == 1 and bat.starts.tolist() == [0, n]
+    for field in ('keys', 'perm', 'd', 'lo', 'hi', 'left', 'right', 'order', 'cross_order'):
+        assert np.array_equal(_np(getattr(one, field)), _np(getattr(bat, field))), field
+    assert one.offsets.numel() == 130 and np.array_equal(_np(one.offsets), _np(bat.offsets))
+    assert np.array_equal(one.bucket, bat.bucket[0]) and np.array_equal(one.cross, bat.cross)
+    n_tok = 3 * (n - 1)
+    for ql, qc in ((0, 0), (4, 9)):
+        for form in ops.RAHT_FORMS:
+            H, dc = ops.raht_forward(one, rgb, form=form)
+            H_b, dc_b = ops.raht_forward_batch(bat, rgb, form=form)
+            assert np.array_equal(_np(H), _np(H_b)) and np.array_equal(_np(dc), _np(dc_b)[0]), (form, 'forward')
+        tok, ctx, esc, hist = ops.raht_quantize(one, H, ql, qc)
+        tok_b, ctx_b, esc_b, hist_b = ops.raht_quantize_batch(bat, H_b, [ql], [qc])
+        E = int(_np(hist)[:, ops.RAHT_ESCAPE].sum())
+        assert esc.numel() == E and (E > 0 or ql > 0 or n < T)                       # (quantiser 0 on random colours escapes)
+        assert np.array_equal(_np(tok), _np(tok_b)) and np.array_equal(_np(ctx), _np(ctx_b)) and tok.numel() == n_tok
+        assert np.array_equal(_np(esc), _np(esc_b)[:E]) and np.array_equal(_np(hist), _np(hist_b)[0]) and tuple(hist_b.shape) == (1, 48, 64)
+        Hh = ops.raht_dequantize(one, tok, esc, ql, qc)
+        Hh_b = ops.raht_dequantize_batch(bat, tok_b, esc_b[:E], [E], [ql], [qc])
+        assert np.array_equal(_np(Hh), _np(Hh_b))
+        for form in ops.RAHT_FORMS:
+            got = ops.raht_inverse(one, Hh, dc.tolist(), form=form)
+            got_b = ops.raht_inverse_batch(bat, Hh_b, _np(dc_b), form=form)
+            assert np.array_equal(_np(got), _np(got_b)), (form, 'inverse')
+        if ql == 0:
+            assert np.array_equal(_np(got), _np(rgb))
+        _, table = at.frequency_rows(_np(hist))
+        for chunk_steps in (1, 3, 0):
+            payload = ops.attr_rans_encode(table, ctx, tok, chunk_steps or max(1, ops.attr_rans_chunks(n_tok, 1)))
+            assert ops.attr_rans_encode_batch(table[None], ctx_b, tok_b, bat.tok, chunk_steps) == [payload], chunk_steps
+            dec, n_escape = ops.attr_rans_decode(table, one, payload, n_tok)
+            dec_b, n_escape_b = ops.attr_rans_decode_batch(table[None], bat, [payload])
+            assert np.array_equal(_np(dec), _np(dec_b)) and np.array_equal(_np(dec), _np(tok)) and [n_escape] == n_escape_b.tolist() == [E]
+
+
+@pytest.mark.parametrize('rows, first', [(3, 0), (3, 3), (257, 0), (257, 3)])
+def test_a_batch_index_in_a_single_frame_touches_nothing_else(rows, first):
+    """rows whose batch column is 1, 5, 15 or -1 are refused by the single entry, and neither its two-int status nor any other guarded
+    allocation is written outside its bounds: such a row must not enter the key's frame bits, which index the duplicate counters"""
+    coords = AT._coords(AT._random_cloud(rows, 32, rows))
+    coords[:, 0] = torch.from_numpy(np.roll(np.resize(np.array([1, 5, 15, -1], np.int32), rows + 4), -first)[:rows]).to(DEV)
+    assert set(_np(coords[:, 0]).tolist()) >= ({1, 5, 15} if first == 0 and rows == 3 else {-1, 1, 5})
+    arena = SA.Arena()
+    with SA.installed(arena):
+        with pytest.raises(ValueError, match='one frame'):
+            ops.raht_tree(coords)
+    torch.cuda.synchronize()
+    assert len(arena.blocks) > 0
+    arena.finish()
+    arena.check()
+
+
 # ---- files cross over ------------------------------------------------------------------------------------------------------------------------
 def test_files_of_encode_and_encode_batch_are_read_by_either(tmp_path):
     frames = [_frame(_small(80, 11, 32), seed=11), _frame(_small(100, 12, 32), seed=12), _frame(_small(1, 13, 32), seed=13),
