@@ -365,6 +365,11 @@ int pcgc_bce_logits(const float* logits, int64_t ld, int64_t n, const uint8_t* t
 size_t pcgc_occ_workspace_bytes(int64_t n);
 int pcgc_occ_symbols(const float* logits, int64_t ld, int64_t n, const uint8_t* truth /*[dev n] or NULL*/, uint16_t* packed /*[dev n]*/,
                      int64_t* sums /*[dev 2] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
+/* the same pass over the nseg (1 .. 16) contiguous frames of a batch's level: frame f is the next seg_rows[f] rows (seg_rows [host nseg]; a
+ * frame may be empty).  packed is what pcgc_occ_symbols writes for the whole level; sums [dev nseg][2] = every frame's pair, each equal to
+ * pcgc_occ_symbols of that frame alone (integer adds: exact in any order; no workspace).  truth = sums = NULL: contexts only. */
+int pcgc_occ_symbols_segments(const float* logits, int64_t ld, int nseg, const int64_t* seg_rows /*[host nseg]*/, const uint8_t* truth /*[dev n] or NULL*/,
+                              uint16_t* packed /*[dev n]*/, int64_t* sums /*[dev nseg,2] or NULL*/, void* stream);
 /* the library's copy of the format tables: P1 uint16 [353], COST int32 [353][2] (either may be NULL) -> number of contexts.  HOST. */
 int pcgc_occ_tables(uint16_t* p1, int32_t* cost);
 
@@ -398,6 +403,26 @@ int pcgc_occ_rans_encode(const uint16_t* packed /*[dev n]*/, int64_t n, int step
  * -> mask [dev n] (0 empty, 1 occupied); host2 [host 2] = occupied rows, unsound chunks (0: the payload is sound), in one small copy. */
 int pcgc_occ_rans_decode(const uint16_t* packed /*[dev n]*/, int64_t n, const uint8_t* payload, int64_t payload_bytes, int steps,
                          uint8_t* mask /*[dev n]*/, int64_t* host2, void* workspace, size_t workspace_bytes, void* stream);
+/* A batch of 1 .. 16 frames (the items of a collated batch at one decoder level) in ONE launch sequence.  Frame f is rows
+ * row[f] .. row[f + 1] of packed and of mask (row [host frames + 1], ascending from 0, below 2^31; any row counts, a frame may be empty) and
+ * is cut into K_f = ceil(rows_f / (64 steps[f])) chunks from its own first row: chunks never straddle frames, the launch has sum K_f
+ * single-wave workgroups.  Its payload is exactly the layout above — what pcgc_occ_rans_encode writes for that frame alone at steps[f] — at
+ * byte pay[f] (a multiple of 8) of the payload buffer; a frame without rows has the 8-byte head S | 0.  The single entries run the same
+ * kernels and host bodies at frames = 1.  workspace: pcgc_occ_rans_batch_workspace_bytes(n, sum K_f) device bytes, 8-byte aligned; the
+ * decoder uses its first 384 + 8 ceil(K / 2) bytes only and accepts as little.  Every entry refuses (-2) before anything is launched. */
+int64_t pcgc_occ_rans_batch_workspace_bytes(int64_t n, int64_t chunks);
+/* steps [host frames] in 1 .. 2^24; pay [host frames + 1]: frame f's room pay[f + 1] - pay[f] >= 8 + 516 K_f + 4 rows_f; sums: NULL or
+ * pcgc_occ_symbols_segments' [dev frames,2].  host [host 3 frames] = every frame's payload bytes, then every frame's sums[0], then every
+ * frame's sums[1] (0 without sums): ONE small synchronising copy.  The finished payloads stay on the device for the caller to fetch. */
+int pcgc_occ_rans_encode_batch(const uint16_t* packed /*[dev n]*/, int frames, const int64_t* row, const int32_t* steps, const int64_t* sums,
+                               uint8_t* payload, const int64_t* pay, int64_t* host, void* workspace, size_t workspace_bytes, void* stream);
+/* steps [host frames]: the S of the frame's head, or 0 for a frame that is not decoded here (its slice of mask is left alone and pay /
+ * pay_bytes of it are not read); pay_bytes [host frames]: the frame's payload bytes, whose head and lengths the caller has checked as for
+ * pcgc_occ_rans_decode.  No access leaves a frame's own payload, whatever its bytes say.  host [host 2 frames] = every frame's occupied
+ * rows, then every frame's unsound chunks (0: sound), in one small copy. */
+int pcgc_occ_rans_decode_batch(const uint16_t* packed /*[dev n]*/, int frames, const int64_t* row, const int32_t* steps, const uint8_t* payload,
+                               const int64_t* pay, const int64_t* pay_bytes, uint8_t* mask /*[dev n]*/, int64_t* host, void* workspace,
+                               size_t workspace_bytes, void* stream);
 
 /* ---- backward pass of the training graph (trainer.py:127-134 `sum_loss.backward()`; csrc/grad.hip).  None of this is on the encode/decode
  *      path.  No floating-point atomics: every reduction has a fixed order (per-workgroup partials in `workspace`, added in ascending

@@ -96,6 +96,10 @@ SIGNATURES = {
     'pcgc_occ_rans_workspace_bytes': (sz, [i64, ci]),
     'pcgc_occ_rans_encode': (ci, [vp, i64, ci, vp, vp, sz, vp, vp, sz, vp]),
     'pcgc_occ_rans_decode': (ci, [vp, i64, vp, i64, ci, vp, vp, vp, sz, vp]),
+    'pcgc_occ_symbols_segments': (ci, [vp, i64, ci, vp, vp, vp, vp, vp]),
+    'pcgc_occ_rans_batch_workspace_bytes': (i64, [i64, i64]),
+    'pcgc_occ_rans_encode_batch': (ci, [vp, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'pcgc_occ_rans_decode_batch': (ci, [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     'pcgc_attr_rans_workspace_bytes': (i64, [i64, ci]),
     'pcgc_attr_rans_encode': (ci, [vp, vp, vp, i64, ci, vp, sz, vp, vp, sz, vp]),
     'pcgc_attr_rans_decode': (ci, [vp, vp, i64, vp, i64, ci, vp, vp, vp, sz, vp]),

@@ -529,6 +529,15 @@ class Coder():
             return self._decode_batch(list(postfixes), rho, dev)
 
     def _decode_batch(self, postfixes, rho, dev):
+        y, counts = self._decode_batch_latent(postfixes, dev)
+        budgets = [[c[0] for c in counts], [c[1] for c in counts], [int(rho * c[2]) for c in counts]]     # coder.py:105-108
+        _, out = self.model.decoder(y, nums_list=budgets, ground_truth_list=[None] * 3, training=False)
+        return self._split_items(out)
+
+    def _decode_batch_latent(self, postfixes, dev, on_rows=None):
+        """the host stages of decode_batch and the batch's latent -> (y on the sorted stride-8 level, items contiguous, the (n4, n2, n1) of
+        every item).  on_rows(rows8), when given, is called with the items' latent rows once the host knows them, before the batch's
+        level is uploaded (lossless.LosslessCoder.decode_batch checks its own files against them there)."""
         B = len(postfixes)
         _check_batch_size(B, 'decode_batch')
 
@@ -548,6 +557,8 @@ class Coder():
                 offs = np.concatenate([[0], np.cumsum(rows)])
                 items = [(None, tuple(int(v) for v in counts[b]), sym_all[offs[b]:offs[b + 1]], np.float32(ranges[b, 0])) for b in range(B)]
                 rows8 = [int(r) for r in rows]
+                if on_rows is not None:
+                    on_rows(rows8)
                 y_C = self._upload_level(int(rows.sum()), dev)
         if items is None:
             def one(b):
@@ -560,6 +571,8 @@ class Coder():
             items = list(_batch_pool().map(one, range(B)))
         if items[0][0] is not None:                                            # (items decoded one by one: assemble and sort here)
             rows8 = [len(it[0]) for it in items]
+            if on_rows is not None:
+                on_rows(rows8)
             C4 = np.zeros((sum(rows8), 4), dtype=np.int32)
             off = 0
             for b, (xyz8, _, _, _) in enumerate(items):
@@ -576,9 +589,11 @@ class Coder():
             off += rows8[b]
         lvl8 = CoordMap(y_C, 8, unique=True)
         lvl8._batch_rows = rows8
-        y = SparseTensor(features=y_F, coordinate_map=lvl8)
-        budgets = [[it[1][0] for it in items], [it[1][1] for it in items], [int(rho * it[1][2]) for it in items]]     # coder.py:105-108
-        _, out = self.model.decoder(y, nums_list=budgets, ground_truth_list=[None] * 3, training=False)
+        return SparseTensor(features=y_F, coordinate_map=lvl8), [it[1] for it in items]
+
+    @staticmethod
+    def _split_items(out):
+        """a decoded batch -> its items, each with batch column 0"""
         outs, off = [], 0
         for b, r in enumerate(out.cmap.batch_rows):
             c = out.C[off:off + r].clone()

@@ -7,7 +7,8 @@
 //
 // One streaming pass, four consecutive rows per thread: 16 B of logits and 4 B of truth in, 8 B out per thread where the logits are dense
 // and the pointers aligned, scalar accesses of the same rows otherwise.  The sums are integers: per-block partials in a slab, added by
-// one block (loss.hip's scheme); the grid is a function of n alone.
+// one block (loss.hip's scheme); the grid is a function of n alone.  pcgc_occ_symbols_segments is the same pass over the contiguous frames
+// of a batch's level, with one pair of sums per frame (k_occ_symbols_segments below).
 #include "pcgc_common.h"
 #include "occupancy_tables.h"
 
@@ -25,18 +26,10 @@ __device__ static inline int occ_context(float z) {
     return (int)rintf(c) + PCGC_OCC_QMAX;                // the bounds are integers: clamping first rounds to the same integer
 }
 
+// A thread's OCC_ROWS consecutive rows from i0 (m of them exist): logits and truth in, ctx << 1 | bit out; ctx[] and bit[] stay with the caller
 template <bool VEC>
-__global__ void __launch_bounds__(OCC_BLOCK) k_occ_symbols(const float* __restrict__ logits, int64_t ld, int64_t n, const uint8_t* __restrict__ truth,
-                                                           uint16_t* __restrict__ packed,
-                                                           uint32_t* __restrict__ cslab, unsigned long long* __restrict__ bslab) {
-    __shared__ int32_t sh_cost[2 * PCGC_OCC_CONTEXTS];
-    __shared__ unsigned cred[OCC_BLOCK / 64];
-    __shared__ unsigned long long bred[OCC_BLOCK / 64];
-    if (truth)                                           // (uniform across the grid)
-        for (int i = threadIdx.x; i < 2 * PCGC_OCC_CONTEXTS; i += OCC_BLOCK) sh_cost[i] = d_occ_cost[i];
-    __syncthreads();
-    const int64_t i0 = ((int64_t)blockIdx.x * OCC_BLOCK + threadIdx.x) * OCC_ROWS;
-    const int m = i0 >= n ? 0 : (int)(n - i0 < OCC_ROWS ? n - i0 : OCC_ROWS);
+__device__ static inline void occ_thread_rows(const float* __restrict__ logits, int64_t ld, const uint8_t* __restrict__ truth, uint16_t* __restrict__ packed,
+                                              int64_t i0, int m, int (&ctx)[OCC_ROWS], int (&bit)[OCC_ROWS]) {
     float x[OCC_ROWS] = {0.f, 0.f, 0.f, 0.f};
     uint8_t y[OCC_ROWS] = {0, 0, 0, 0};
     if (VEC && m == OCC_ROWS) {
@@ -50,20 +43,36 @@ __global__ void __launch_bounds__(OCC_BLOCK) k_occ_symbols(const float* __restri
         }
     }
     uint16_t w[OCC_ROWS] = {0, 0, 0, 0};
-    unsigned occupied = 0;
-    unsigned long long bits = 0;
     for (int j = 0; j < m; ++j) {
-        const int ctx = occ_context(x[j]);
-        const int b = y[j] != 0;
-        w[j] = (uint16_t)((ctx << 1) | b);
-        if (truth) { occupied += (unsigned)b; bits += (unsigned long long)sh_cost[2 * ctx + b]; }
+        ctx[j] = occ_context(x[j]);
+        bit[j] = y[j] != 0;
+        w[j] = (uint16_t)((ctx[j] << 1) | bit[j]);
     }
     if (VEC && m == OCC_ROWS) {
         *(ushort4*)(packed + i0) = make_ushort4(w[0], w[1], w[2], w[3]);
     } else {
         for (int j = 0; j < m; ++j) packed[i0 + j] = w[j];
     }
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(OCC_BLOCK) k_occ_symbols(const float* __restrict__ logits, int64_t ld, int64_t n, const uint8_t* __restrict__ truth,
+                                                           uint16_t* __restrict__ packed,
+                                                           uint32_t* __restrict__ cslab, unsigned long long* __restrict__ bslab) {
+    __shared__ int32_t sh_cost[2 * PCGC_OCC_CONTEXTS];
+    __shared__ unsigned cred[OCC_BLOCK / 64];
+    __shared__ unsigned long long bred[OCC_BLOCK / 64];
+    if (truth)                                           // (uniform across the grid)
+        for (int i = threadIdx.x; i < 2 * PCGC_OCC_CONTEXTS; i += OCC_BLOCK) sh_cost[i] = d_occ_cost[i];
+    __syncthreads();
+    const int64_t i0 = ((int64_t)blockIdx.x * OCC_BLOCK + threadIdx.x) * OCC_ROWS;
+    const int m = i0 >= n ? 0 : (int)(n - i0 < OCC_ROWS ? n - i0 : OCC_ROWS);
+    int ctx[OCC_ROWS], bit[OCC_ROWS];
+    occ_thread_rows<VEC>(logits, ld, truth, packed, i0, m, ctx, bit);
     if (!truth) return;                                  // decoder side: contexts only
+    unsigned occupied = 0;
+    unsigned long long bits = 0;
+    for (int j = 0; j < m; ++j) { occupied += (unsigned)bit[j]; bits += (unsigned long long)sh_cost[2 * ctx[j] + bit[j]]; }
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) { occupied += __shfl_xor(occupied, d, 64); bits += __shfl_xor(bits, d, 64); }
     if ((threadIdx.x & 63) == 0) { cred[threadIdx.x >> 6] = occupied; bred[threadIdx.x >> 6] = bits; }
@@ -73,6 +82,58 @@ __global__ void __launch_bounds__(OCC_BLOCK) k_occ_symbols(const float* __restri
         for (int k = 0; k < OCC_BLOCK / 64; ++k) { c += cred[k]; b += bred[k]; }
         cslab[blockIdx.x] = c; bslab[blockIdx.x] = b;
     }
+}
+
+// The same pass over nseg contiguous frames (a batch's level: frame f is rows row[f] .. row[f + 1]); the table travels by value.  packed is
+// what k_occ_symbols writes (the grid and every thread's rows are the same: a context depends on its own logit only); the sums are per frame.
+// A block of 1024 rows may hold the end of one frame, several whole small ones and the start of another: each block adds its rows into
+// per-frame accumulators in LDS (a wave whose rows all lie in one frame reduces by shuffles first) and then adds them to sums [nseg, 2] with
+// one integer atomic per frame it touches.  Integer sums: exact, whatever the order the blocks arrive in.  Nothing is read back in this launch.
+constexpr int OCC_MAX_SEGMENTS = 16;
+struct OccSegments {
+    long long row[OCC_MAX_SEGMENTS + 1];                 // ascending from 0; row[f] = row[nseg] for f > nseg
+    int nseg;
+};
+__device__ static inline int occ_segment_of(const OccSegments& sg, int64_t i) {       // the frame that holds row i < row[nseg] (frames may be empty)
+    int f = 0;
+    for (int b = 1; b < OCC_MAX_SEGMENTS; ++b) f += (b < sg.nseg && (int64_t)sg.row[b] <= i) ? 1 : 0;
+    return f;
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(OCC_BLOCK) k_occ_symbols_segments(const float* __restrict__ logits, int64_t ld, OccSegments sg, const uint8_t* __restrict__ truth,
+                                                                    uint16_t* __restrict__ packed, unsigned long long* __restrict__ sums) {
+    __shared__ int32_t sh_cost[2 * PCGC_OCC_CONTEXTS];
+    __shared__ unsigned long long acc[OCC_MAX_SEGMENTS][2];
+    for (int i = threadIdx.x; i < 2 * PCGC_OCC_CONTEXTS; i += OCC_BLOCK) sh_cost[i] = d_occ_cost[i];
+    if (threadIdx.x < 2 * OCC_MAX_SEGMENTS) acc[threadIdx.x >> 1][threadIdx.x & 1] = 0ull;
+    __syncthreads();
+    const int64_t n = sg.row[OCC_MAX_SEGMENTS];
+    const int64_t i0 =((int64_t)blockIdx.x * OCC_BLOCK + threadIdx.x) * OCC_ROWS;
+    const int m = i0 >= n ? 0 : (int)(n - i0 < OCC_ROWS ? n - i0 : OCC_ROWS);
+    int ctx[OCC_ROWS], bit[OCC_ROWS];
+    occ_thread_rows<VEC>(logits, ld, truth, packed, i0, m, ctx, bit);
+    // the frames of this thread's first and last row; a thread without rows sides with its wave's first lane
+    const int f_lo = m ? occ_segment_of(sg, i0) : -1, f_hi = m ? occ_segment_of(sg, i0 + m - 1) : -1;
+    const int f_wave = __shfl(f_lo, 0, 64);
+    const bool one_frame = __all(m == 0 || (f_lo == f_wave && f_hi == f_wave));       // (lane 0 has rows whenever any lane of its wave has)
+    if (one_frame) {
+        unsigned long long occupied = 0, bits = 0;
+        for (int j = 0; j < m; ++j) { occupied += (unsigned long long)bit[j]; bits += (unsigned long long)sh_cost[2 * ctx[j] + bit[j]]; }
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) { occupied += __shfl_xor(occupied, d, 64); bits += __shfl_xor(bits, d, 64); }
+        if ((threadIdx.x & 63) == 0 && f_wave >= 0) { atomicAdd(&acc[f_wave][0], occupied); atomicAdd(&acc[f_wave][1], bits); }
+    } else {
+        for (int j = 0; j < m; ++j) {
+            const int f = occ_segment_of(sg, i0 + j);
+            if (bit[j]) atomicAdd(&acc[f][0], 1ull);
+            atomicAdd(&acc[f][1], (unsigned long long)sh_cost[2 * ctx[j] + bit[j]]);
+        }
+    }
+    __syncthreads();
+    // one global add per non-zero accumulator, i.e. per frame this block's rows lie in (integers: the order of arrival does not matter)
+    if (threadIdx.x < 2 * OCC_MAX_SEGMENTS && acc[threadIdx.x >> 1][threadIdx.x & 1])
+        atomicAdd(&sums[threadIdx.x], acc[threadIdx.x >> 1][threadIdx.x & 1]);
 }
 // second stage: one block; thread t adds slots t, t + 256, ... (integers: the order does not matter, the result is exact)
 __global__ void __launch_bounds__(OCC_BLOCK) k_occ_final(const uint32_t* __restrict__ cslab, const unsigned long long* __restrict__ bslab, int64_t blocks,
@@ -130,5 +191,33 @@ extern "C" int pcgc_occ_symbols(const float* logits, int64_t ld, int64_t n, cons
         hipLaunchKernelGGL(k_occ_final, dim3(1), dim3(OCC_BLOCK), 0, S(stream), cslab, bslab, blocks, (long long*)sums);
         PCGC_CHECK_LAUNCH("occ_symbols");
     }
+    return 0;
+}
+
+extern "C" int pcgc_occ_symbols_segments(const float* logits, int64_t ld, int nseg, const int64_t* seg_rows, const uint8_t* truth, uint16_t* packed,
+                                         int64_t* sums, void* stream) {
+    PCGC_REQUIRE(nseg >= 1 && nseg <= OCC_MAX_SEGMENTS && seg_rows && ld >= 1, "1 to 16 segments");
+    OccSegments sg;
+    sg.nseg = nseg;
+    sg.row[0] = 0;
+    for (int f = 0; f < OCC_MAX_SEGMENTS; ++f) {
+        PCGC_REQUIRE(f >= nseg || seg_rows[f] >= 0, "negative row count");
+        sg.row[f + 1] = sg.row[f] + (f < nseg ? seg_rows[f] : 0);
+        PCGC_REQUIRE(sg.row[f + 1] < ((int64_t)1 << 31) * OCC_ROWS, "too many rows");
+    }
+    const int64_t n = sg.row[nseg];
+    PCGC_REQUIRE(n == 0 || !truth == !sums, "truth and sums go together (both for the encoder, neither for the decoder)");
+    if (!truth || n == 0) {                              // contexts only, or no rows (then there may be no truth pointer to go with sums)
+        if (sums) { hipError_t e = hipMemsetAsync(sums, 0, 2 * nseg * sizeof(int64_t), S(stream)); if (e != hipSuccess) { pcgc_set_error("occ_symbols_segments: %s", hipGetErrorString(e)); return -1; } }
+        return n ? pcgc_occ_symbols(logits, ld, n, nullptr, packed, nullptr, nullptr, 0, stream) : 0;
+    }
+    PCGC_REQUIRE(logits && packed, "null argument");
+    hipError_t e = hipMemsetAsync(sums, 0, 2 * nseg * sizeof(int64_t), S(stream));
+    if (e != hipSuccess) { pcgc_set_error("occ_symbols_segments: %s", hipGetErrorString(e)); return -1; }
+    const int64_t blocks = occ_blocks(n);
+    const bool vec = ld == 1 && (((uintptr_t)logits) & 15) == 0 && (((uintptr_t)truth) & 3) == 0 && (((uintptr_t)packed) & 7) == 0;
+    if (vec) hipLaunchKernelGGL(k_occ_symbols_segments<true>, dim3((unsigned)blocks), dim3(OCC_BLOCK), 0, S(stream), logits, ld, sg, truth, packed, (unsigned long long*)sums);
+    else hipLaunchKernelGGL(k_occ_symbols_segments<false>, dim3((unsigned)blocks), dim3(OCC_BLOCK), 0, S(stream), logits, ld, sg, truth, packed, (unsigned long long*)sums);
+    PCGC_CHECK_LAUNCH("occ_symbols_segments");
     return 0;
 }

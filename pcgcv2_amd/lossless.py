@@ -26,7 +26,15 @@ must be consumed and all 64 lanes must end at their initial state 2^31.  The tab
 extensions are refused; damage inside a chunk's words escapes when the lanes that read it still end at 2^31 with the word count intact —
 unlikely (a damaged lane has to land on one value of 2^32 and more), not impossible.  A decoder that needs certainty asks for version 1.
 
+Batches.  `encode_batch`, `estimate_batch` and `decode_batch` code the items of a collated batch (sequences, the octant blocks of a large
+cloud) in one pass: Coder.encode_batch / the batch's latent, then the decoder network ONCE per level on the batch, whose levels are the
+concatenation of the items' levels.  Item b's candidates of a level are a contiguous run of rows, so ops.occ_symbols_segments keeps one
+pair of sums per item and the device coder (ops.occ_rans_encode_batch / occ_rans_decode_batch) one payload per item, its chunks beside the
+other items' in the same launches, never straddling items.  Every file is byte for byte what `encode` of the item alone writes, in both
+versions and at every `chunk_steps`; a decode_batch may mix versions, and either side reads the other's files.
+
     python -m pcgcv2_amd.lossless --ckptdir CKPT --filedir CLOUD.ply [--outdir DIR] [--occupancy_coder {host,device}] [--chunk_steps S]
+    python -m pcgcv2_amd.lossless --ckptdir CKPT --filedir A.ply B.ply C.ply ...      up to 16 files, coded as one batch
 """
 import os
 import struct
@@ -37,7 +45,7 @@ import torch
 
 from . import occupancy_model, ops
 from ._lib import PcgcError
-from .coder import Coder, _dump, _slurp, stream_bits, STREAMS
+from .coder import Coder, _batch_pool, _check_batch_size, _dump, _slurp, stream_bits, STREAMS
 from .data_utils import isin_mask
 from .sparse import CoordMap, SparseTensor, require_gpu
 
@@ -52,7 +60,8 @@ LEVELS = 3
 
 
 class LosslessCoder():
-    """Coder(model, filename) plus the occupancy stream.  One frame per call.  occupancy_coder: 'host' writes version 1 (the host range
+    """Coder(model, filename) plus the occupancy stream.  encode / estimate / decode: one frame per call; the _batch methods: a collated
+    batch.  occupancy_coder: 'host' writes version 1 (the host range
     coder), 'device' version 2 (rANS on the device) in chunks of 64 x chunk_steps rows (None: CHUNK_STEPS; 0: one chunk per level)."""
 
     def __init__(self, model, filename, occupancy_coder='host', chunk_steps=None):
@@ -88,7 +97,14 @@ class LosslessCoder():
             raise PcgcError(f'{len(lvl8)} stride-8 coordinates but {sym_d.shape[0]} latent rows')
         if len(lvl8) and lvl8._prepared_up is None:
             lvl8.prepare_up()
-        return SparseTensor(features=ops.desymbolize(sym_d, min_v), coordinate_map=lvl8)
+        if not isinstance(min_v, (list, tuple)):
+            return SparseTensor(features=ops.desymbolize(sym_d, min_v), coordinate_map=lvl8)
+        # a batch: every item has its own symbol offset (Coder._decode_batch_latent builds the same rows on the decoder's side)
+        feats, off = torch.empty(sym_d.shape, dtype=torch.float32, device=sym_d.device), 0
+        for rows, lo in zip(lvl8.batch_rows, min_v):
+            feats[off:off + rows] = ops.desymbolize(sym_d[off:off + rows], lo)
+            off += rows
+        return SparseTensor(features=feats, coordinate_map=lvl8)
 
     def _logits(self, out, l):
         """decoder level l up to its classification head -> (candidates with their features, logits [8 n, 1])"""
@@ -188,6 +204,103 @@ class LosslessCoder():
             y = SparseTensor(ops.gather_feats(y_list[0].F, order), coordinate_map=CoordMap(ops.gather_coords(lvl8.C, order), lvl8.stride, unique=True))
             return self._enhance(x, y, code=False)[0]['est_bits_O']
 
+    # ---- encoder, collated batches -------------------------------------------------------------------------------------
+    # B clouds through ONE pass: Coder.encode_batch, then the decoder network once per level on the batch.  A level's candidates are 8 per
+    # parent in parent order, so item b is the contiguous rows [row[b], row[b + 1]); the batch index is part of every coordinate, so the truth
+    # mask is per item; ops.occ_symbols_segments and ops.occ_rans_encode_batch keep one pair of sums and one payload per item.  Every file is
+    # byte for byte what encode() of the item alone writes: a context depends on its own logit, a logit on its own item's rows only.
+    def _enhance_batch(self, x, y, code):
+        """_enhance over a collated batch -> (one record per item, one list of three payloads per item, or None)"""
+        dev = x.device
+        t = self._tick(None, 0.0, dev)
+        _, truths = self._truth_levels(x)
+        B = len(y.cmap.batch_rows)
+        ranges, sym_h = ops.quantize_symbols_segments(y.F, y.cmap.batch_rows)
+        out = self._latent_level(torch.from_numpy(sym_h).to(dev), [lo for lo, _ in ranges], y.cmap)
+        t = self._tick('copies', t, dev)
+        on_device = code and self.occupancy_coder == 'device'
+        records = [{'est_units_O': 0, 'rows': []} for _ in range(B)]
+        payloads, pending = [[] for _ in range(B)], []
+        for l in range(LEVELS):
+            out, logits = self._logits(out, l)
+            truth = isin_mask(out.cmap.C, truths[l])
+            t = self._tick('network', t, dev)
+            rows, want = out.cmap.batch_rows, truths[l].batch_rows
+            packed, sums = ops.occ_symbols_segments(logits, rows, truth)
+            t = self._tick('k_occ_symbols', t, dev)
+            if on_device:                         # the words and the finished payloads stay on the device; lengths and counts come in one small copy
+                lay = ops.occ_rans_batch_layout(rows, self.chunk_steps)
+                coded, occupied, cost = ops.occ_rans_encode_batch(packed, rows, self.chunk_steps, sums, fetch=False)
+                t = self._tick('k_occ_rans_encode', t, dev)
+            else:
+                words, occupied, cost = ops.occ_words_host_segments(packed, sums)
+                t = self._tick('copies', t, dev)
+            for b in range(B):
+                if occupied[b] != want[b]:
+                    raise PcgcError(f'lossless encode_batch: item {b}: level {l} holds {want[b]} voxels but {int(occupied[b])} of its {rows[b]} '
+                                    'candidates are among them: the item is not a set of distinct voxels of one frame')
+                records[b]['rows'].append(int(rows[b]))
+                records[b]['est_units_O'] += int(cost[b])
+                if on_device:
+                    records[b].setdefault('chunks', []).append(int(lay['chunks'][b]))
+            if on_device:
+                pending.append(coded)
+            elif code:
+                edge = np.concatenate([[0], np.cumsum(rows)])
+                coded = list(_batch_pool().map(lambda b: ops.rc_encode_ctx(self._cdf, words[edge[b]:edge[b + 1]] >> 1, words[edge[b]:edge[b + 1]] & 1),
+                                               range(B)))
+                for b in range(B):
+                    payloads[b].append(coded[b])
+                t = self._tick('host coder', t)
+            out = self.model.decoder.pruning(out, truth, n_keep=int(sum(want)), keep_per_item=list(want))
+            t = self._tick('network', t, dev)
+        if pending:                               # the three levels' payloads in one copy, after the last level's launches
+            for level in ops.occ_rans_payloads(pending):
+                for b in range(B):
+                    payloads[b].append(level[b])
+            t = self._tick('copies', t, dev)
+        for r in records:
+            r['est_bits_O'] = r['est_units_O'] / occupancy_model.COST_UNIT
+        return records, payloads if code else None
+
+    @torch.no_grad()
+    def encode_batch(self, x, postfixes):
+        """x: collated sparse tensor (item index in column 0, items contiguous, 1 to coder.MAX_BATCH_ITEMS items); postfixes[b]: file postfix
+        of item b.  Coder.encode_batch(x, postfixes), then one `_O.bin` per item -> a list of encode()'s records.  Every file is byte for byte
+        what encode() of the item alone writes.  PcgcError naming the item whose occupied count disagrees with its truth level."""
+        postfixes = _check_items(x, postfixes, 'encode_batch')
+        with torch.cuda.device(x.device):
+            t = self._tick(None, 0.0, x.device)
+            if len(x.cmap.batch_rows) != len(postfixes):
+                raise ValueError(f'encode_batch: {len(postfixes)} postfixes for a batch of {len(x.cmap.batch_rows)} items')
+            y = self.coder.encode_batch(x, postfixes)
+            self._tick('lossy encode', t, x.device)
+            records, payloads = self._enhance_batch(x, y, code=True)
+            t = self._tick(None, 0.0)
+            for record, mine, postfix in zip(records, payloads, postfixes):
+                sizes = [v for r, p in zip(record['rows'], mine) for v in (r, len(p))]
+                blob = _HEAD.pack(MAGIC, CODERS[self.occupancy_coder], occupancy_model.table_crc()) + _LEVELS.pack(*sizes) + b''.join(mine)
+                _dump(self.filename + postfix + SUFFIX, blob)
+                record['bits_O'] = 8 * len(blob)
+                record['payload_bytes'] = [len(p) for p in mine]
+            self._tick('host coder', t)
+        return records
+
+    @torch.no_grad()
+    def estimate_batch(self, x):
+        """est_bits_O of every item of a collated batch, each equal to estimate() of the item alone, without writing anything"""
+        _check_items(x, None, 'estimate_batch')
+        with torch.cuda.device(x.device):
+            xi, _ = self._truth_levels(x)
+            lvl8 = xi.cmap.build_pyramid(3)
+            _check_batch_size(len(lvl8.batch_rows), 'estimate_batch')
+            y_list = self.model.encoder(xi)
+            order = ops.sort_zyx(lvl8.C, batch_major=True)                   # (the order Coder.encode_batch codes the latent in)
+            cmap = CoordMap(ops.gather_coords(lvl8.C, order), lvl8.stride, unique=True)
+            cmap._batch_rows = list(lvl8.batch_rows)
+            y = SparseTensor(ops.gather_feats(y_list[0].F, order), coordinate_map=cmap)
+            return [r['est_bits_O'] for r in self._enhance_batch(x, y, code=False)[0]]
+
     # ---- decoder ------------------------------------------------------------------------------------------------------------------------
     def _read_stream(self, postfix):
         """-> (candidate rows, payloads) of the three levels, of either version"""
@@ -269,6 +382,94 @@ class LosslessCoder():
         return out
 
 
+    # ---- decoder, collated batches --------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def decode_batch(self, postfixes):
+        """reads the files of every item (each `_O.bin` in the version it has) and decodes them in ONE decoder pass -> list of stride-1
+        sparse tensors (batch column 0 each), equal to decode() of the item alone.  Every host check of every item — magic, version, CRC,
+        lengths, the version-2 heads, rows of the first level against the item's latent — runs before the batch's level is uploaded;
+        rows of a later level are checked against the level above once that is decoded.  A refusal names the item's file and the level."""
+        postfixes = _check_items(None, postfixes, 'decode_batch')
+        dev = require_gpu(next(self.model.decoder.parameters()).device)
+        with torch.cuda.device(dev):
+            return self._decode_batch(postfixes, dev)
+
+    def _decode_batch(self, postfixes, dev):
+        t = self._tick(None, 0.0, dev)
+        B = len(postfixes)
+        paths = [self.filename + p + SUFFIX for p in postfixes]
+        streams = [self._read_versioned(p) for p in postfixes]               # (version, rows, payloads) per item, checked
+        for b, (_, rows, _) in enumerate(streams):
+            for l in range(1, LEVELS):                                       # rows of a level = 8 x occupied rows of the level above: at least a multiple of 8
+                if rows[l] % 8:
+                    raise PcgcError(f'{paths[b]}: level {l} declares {rows[l]} candidate rows, not a multiple of 8')
+
+        def against(level, parents):
+            for b in range(B):
+                if streams[b][1][level] != 8 * parents[b]:
+                    raise PcgcError(f'{paths[b]}: level {level} declares {streams[b][1][level]} candidate rows; the level above has '
+                                    f'{parents[b]} voxels, i.e. {8 * parents[b]} candidates')
+
+        out, _ = self.coder._decode_batch_latent(postfixes, dev, on_rows=lambda rows8: against(0, rows8))
+        t = self._tick('host coder', t, dev)
+        device_items = [b for b in range(B) if streams[b][0] == VERSION_DEVICE]
+        host_items = [b for b in range(B) if streams[b][0] != VERSION_DEVICE]
+        parents = list(out.cmap.batch_rows)
+        for l in range(LEVELS):
+            against(l, parents)
+            out, logits = self._logits(out, l)
+            t = self._tick('network', t, dev)
+            rows = out.cmap.batch_rows
+            edge = np.concatenate([[0], np.cumsum(rows)])
+            packed, _ = ops.occ_symbols_segments(logits, rows)
+            mask = torch.empty(int(edge[-1]), dtype=torch.uint8, device=dev)
+            t = self._tick('k_occ_symbols', t, dev)
+            if device_items:                      # one launch sequence for the version-2 items; the bits never reach the host
+                _, occupied = ops.occ_rans_decode_batch(packed, rows, [streams[b][2][l] if streams[b][0] == VERSION_DEVICE else None for b in range(B)],
+                                                        mask=mask, names=[f'{path}: level {l}' for path in paths])
+                parents = [int(v) for v in occupied]
+                t = self._tick('k_occ_rans_decode', t, dev)
+            if host_items:                        # one copy of the contexts down, the items' payloads on the pool, their bits up in one copy
+                words = packed.cpu().numpy().view(np.uint16)
+                t = self._tick('copies', t, dev)
+
+                def one(b):
+                    try:
+                        return ops.rc_decode_ctx(self._cdf, words[edge[b]:edge[b + 1]] >> 1, streams[b][2][l])
+                    except PcgcError as e:
+                        raise PcgcError(f'{paths[b]}: level {l}: {e}') from None
+                bits = list(_batch_pool().map(one, host_items))
+                t = self._tick('host coder', t)
+                up = torch.from_numpy(np.concatenate(bits).astype(np.uint8)).to(dev)
+                at = 0
+                for b, mine in zip(host_items, bits):
+                    mask[edge[b]:edge[b + 1]] = up[at:at + len(mine)]
+                    at += len(mine)
+                    parents[b] = int(mine.sum())
+                t = self._tick('copies', t, dev)
+            for b in range(B):
+                if parents[b] == 0:
+                    raise PcgcError(f'{paths[b]}: level {l} decodes to no voxel at all')
+            out = self.model.decoder.pruning(out, mask, n_keep=sum(parents), keep_per_item=parents)
+            t = self._tick('network', t, dev)
+        return Coder._split_items(out)
+
+
+def _check_items(x, postfixes, what):
+    """the arguments of a batch call that the host can judge -> the postfixes as a list"""
+    if postfixes is not None:
+        postfixes = list(postfixes)
+        _check_batch_size(len(postfixes), what)
+        if len(set(postfixes)) != len(postfixes):
+            raise ValueError(f'{what}: the postfixes name the items\' files and must differ, got {postfixes}')
+    if x is not None or postfixes is None:
+        if not isinstance(x, SparseTensor):
+            raise TypeError('LosslessCoder codes a SparseTensor')
+        if len(x) == 0:
+            raise ValueError('LosslessCoder: an empty cloud')
+    return postfixes
+
+
 def occupancy_bits(prefix, postfix=''):
     """bits of `_O.bin` of one coded cloud"""
     return os.path.getsize(prefix + postfix + SUFFIX) * 8
@@ -325,18 +526,106 @@ def run(ckptdir, filedir, outdir, occupancy_coder='host', chunk_steps=None, attr
     return record
 
 
+def run_batch(ckptdir, filedirs, outdir, occupancy_coder='host', chunk_steps=None, attributes=None, attribute_coder='host'):
+    """several clouds collated into one batch and coded with encode_batch / decode_batch: per file the lines of run and its `_dec.ply`.
+    attributes = (Q, Qc): the files' colours on the decoded voxel sets through AttributeCoder.encode_batch / decode_batch."""
+    from .coder import device, _Stopwatch
+    from .data_utils import load_sparse_tensor, read_ply_ascii_with_colours, write_ply_ascii_geo, write_ply_ascii_geo_rgb
+    from .pcc_model import PCCModel
+    filedirs = list(filedirs)
+    _check_batch_size(len(filedirs), 'run_batch')
+    names = [os.path.split(f)[-1].split('.')[0] for f in filedirs]
+    if len(set(names)) != len(names):
+        raise ValueError(f'{names}: the files of a batch need distinct names, they name the outputs')
+    clouds = [load_sparse_tensor(f, device) for f in filedirs]
+    coords = torch.cat([torch.cat([torch.full_like(x.C[:, :1], b), x.C[:, 1:]], 1) for b, x in enumerate(clouds)]).contiguous()
+    batch = SparseTensor(torch.ones((len(coords), 1), device=device), coordinates=coords, tensor_stride=1, device=device)
+    os.makedirs(outdir, exist_ok=True)
+    prefix = os.path.join(outdir, '')
+    if not os.path.exists(ckptdir):
+        raise FileNotFoundError(ckptdir)
+    model = PCCModel().to(device)
+    model.load_state_dict(torch.load(ckptdir, map_location=device)['model'])
+    print('load checkpoint from \t', ckptdir)
+    coder = LosslessCoder(model=model, filename=prefix, occupancy_coder=occupancy_coder, chunk_steps=chunk_steps)
+    with _Stopwatch('Enc Time'):
+        records = coder.encode_batch(batch, names)
+    with _Stopwatch('Dec Time'):
+        decoded = coder.decode_batch(names)
+    colours = None
+    if attributes is not None:
+        from .attributes import AttributeCoder
+        from .pc_error import colour_psnr_device, lattice_coords, nn_both, recolour_device
+        carried, inputs = [], []
+        for b, f in enumerate(filedirs):
+            xyz, rgb = read_ply_ascii_with_colours(f)
+            if rgb is None:
+                raise ValueError(f'{f} has no colours (red green blue): --attributes needs them')
+            mine = decoded[b].C.detach().contiguous()
+            a, ca = lattice_coords(xyz, device), torch.from_numpy(rgb).to(device)
+            nn = nn_both(a, mine)
+            carried.append(recolour_device(a, ca, mine, nn=nn))
+            inputs.append((a, ca, nn))
+        where = torch.cat([torch.cat([torch.full_like(d.C[:, :1], b), d.C[:, 1:]], 1) for b, d in enumerate(decoded)]).contiguous()
+        attribute_coder_ = AttributeCoder(prefix, attribute_coder=attribute_coder)
+        records_a = attribute_coder_.encode_batch(where, torch.cat(carried), *attributes, postfixes=names)
+        colours = attribute_coder_.decode_batch(where, postfixes=names)
+    wrong, at = [], 0
+    for b, (x, x_dec) in enumerate(zip(clouds, decoded)):
+        stem = prefix + names[b]
+        print(stem)
+        exact = same_voxels(x.C, x_dec.C)
+        bits = np.append(stream_bits(stem), occupancy_bits(stem))
+        bpps = (bits / len(x)).round(3)
+        for name, n_bits, bpp in zip(STREAMS + (SUFFIX,), bits, bpps):
+            print(f'{name}:\t {n_bits} bits\t {bpp} bpp')
+        print('bits:\t', sum(bits), '\nbpps:\t', sum(bpps).round(3))
+        print('ideal bits of _O.bin:\t', round(records[b]['est_bits_O'], 1), '\ncandidate rows:\t', records[b]['rows'])
+        print('lossless:\t', 'exact' if exact else 'MISMATCH')
+        if colours is not None:
+            rgb_dec = colours[at:at + len(x_dec)]
+            at += len(x_dec)
+            a, ca, nn = inputs[b]
+            print('bits _A.bin:\t', records_a[b]['bits_A'], '\nbpp _A.bin:\t', round(records_a[b]['bits_A'] / len(x), 3))
+            print('Colour PSNR (Y):\t', colour_psnr_device(a, ca, x_dec.C.detach().contiguous(), rgb_dec, nn=nn)['c[0],PSNRF'])
+            write_ply_ascii_geo_rgb(stem + '_dec.ply', x_dec.C.detach().cpu().numpy()[:, 1:], rgb_dec.cpu().numpy())
+        else:
+            write_ply_ascii_geo(stem + '_dec.ply', x_dec.C.detach().cpu().numpy()[:, 1:])
+        if not exact:
+            wrong.append(f'{stem} ({len(x_dec)} against {len(x)} voxels)')
+    if wrong:
+        raise PcgcError(f'the decoded voxel set differs from the input: {", ".join(wrong)}')
+    return records
+
+
 def main(argv=None):
     import argparse
     p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument("--ckptdir", default='ckpts/r3_0.10bpp.pth')
-    p.add_argument("--filedir", default='../../../testdata/8iVFB/longdress_vox10_1300.ply')
+    p.add_argument("--filedir", default=['../../../testdata/8iVFB/longdress_vox10_1300.ply'], nargs='+',
+                   help="the cloud; several files (up to 16) are collated and coded as one batch (encode_batch / decode_batch)")
     p.add_argument("--outdir", default='./output')
     p.add_argument("--occupancy_coder", choices=sorted(CODERS), default='host',
                    help="who codes _O.bin: the host range coder (version 1) or interleaved rANS on the device (version 2)")
     p.add_argument("--chunk_steps", type=int, default=None,
                    help="device coder: rows per chunk / 64 (0: one chunk per level); default lossless.CHUNK_STEPS")
+    p.add_argument("--attributes", metavar='Q[,Qc]', default=None,
+                   help="also write _A.bin, the colour stream (attributes.py): the files' colours on the decoded voxel sets, quantiser step Q "
+                        "(Qc for chroma; 0 .. 255, 0: lossless)")
+    p.add_argument("--attribute_coder", choices=('host', 'device'), default='host', help="with --attributes: who codes the payload of _A.bin")
     args = p.parse_args(argv)
-    run(args.ckptdir, args.filedir, args.outdir, args.occupancy_coder, args.chunk_steps)
+    if args.attributes is not None:
+        try:
+            q = [int(v) for v in args.attributes.split(',')]
+            if not 1 <= len(q) <= 2 or not all(0 <= v <= 255 for v in q):
+                raise ValueError
+        except ValueError:
+            p.error(f'--attributes {args.attributes}: Q or Q,Qc with integers in 0 .. 255')
+        args.attributes = (q[0], q[-1])
+    if len(args.filedir) == 1:
+        run(args.ckptdir, args.filedir[0], args.outdir, args.occupancy_coder, args.chunk_steps, args.attributes, args.attribute_coder)
+    else:
+        run_batch(args.ckptdir, args.filedir, args.outdir, args.occupancy_coder, args.chunk_steps, args.attributes, args.attribute_coder)
 
 
 if __name__ == '__main__':

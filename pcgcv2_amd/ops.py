@@ -1204,6 +1204,47 @@ def occ_words_host(packed, sums=None):
     return host[8:].view(np.uint16), int(both[0]), int(both[1])
 
 
+OCC_MAX_FRAMES = 16                                                               # frames of one pcgc_occ_symbols_segments / pcgc_occ_rans_*_batch call
+
+
+def _frame_rows(rows_per_frame, what):
+    rows = np.asarray(rows_per_frame, dtype=np.int64).reshape(-1)
+    if not 1 <= rows.size <= OCC_MAX_FRAMES:
+        raise ValueError(f'{what}: {rows.size} frames; a call takes 1 to {OCC_MAX_FRAMES}')
+    if (rows < 0).any() or int(rows.sum()) >= 1 << 31:
+        raise ValueError(f'{what}: row counts {rows.tolist()} (each >= 0, below 2^31 in all)')
+    return rows
+
+
+def occ_symbols_segments(logits, seg_rows, truth=None):
+    """occ_symbols over the contiguous frames of a batch's level: frame f is the next seg_rows[f] rows -> (packed int16 [n], what occ_symbols
+    gives for the whole level, sums int64 [B, 2] on the device: every frame's pair, equal to occ_symbols of that frame alone).  truth=None:
+    contexts only, (packed, None).  Both are views of ONE buffer, sums first."""
+    rows = _frame_rows(seg_rows, 'occ_symbols_segments')
+    _f32(logits, 'logits')
+    n, dev = logits.shape[0], logits.device
+    if logits.dim() > 2 or (logits.dim() == 2 and logits.shape[1] != 1) or int(rows.sum()) != n:
+        raise PcgcError(f'occ_symbols_segments: logits {tuple(logits.shape)}, expected [n] or [n, 1] with n = {int(rows.sum())}, the frames\' rows')
+    B, ld = rows.size, max(int(logits.stride(0)), 1)
+    buf = torch.empty(8 * B + n, dtype=torch.int16, device=dev)                # [sums as 2 B int64 = 8 B int16 | packed]
+    packed, sums = buf[8 * B:], None
+    if truth is not None:
+        if _dev(truth, torch.uint8, 'truth').shape[0] != n:
+            raise PcgcError(f'occ_symbols_segments: {n} logits against a mask of {truth.shape[0]} rows')
+        sums = buf[:8 * B].view(torch.int64).view(B, 2)
+    check(lib().pcgc_occ_symbols_segments(_p(logits), ld, B, rows.ctypes.data, _p(truth), _p(packed), _p(sums), _stream(logits)), 'occ_symbols_segments')
+    return packed, sums
+
+
+def occ_words_host_segments(packed, sums):
+    """what occ_symbols_segments returned with a truth mask, brought to the host in ONE synchronising copy -> (words uint16 ndarray [n],
+    occupied rows per frame, ideal code length per frame in 2^-16 bit; both int64 ndarrays [B])."""
+    B = sums.shape[0]
+    host = packed._base.cpu().numpy()                                          # [sums | packed]: one buffer (occ_symbols_segments)
+    both = host[:8 * B].view(np.int64).reshape(B, 2)
+    return host[8 * B:].view(np.uint16), both[:, 0].copy(), both[:, 1].copy()
+
+
 def occ_tables():
     """the library's copy of the lossless mode's format tables -> (P1 uint16 [353], COST int32 [353, 2]) (host call)"""
     n = int(lib().pcgc_occ_tables(None, None))
@@ -1283,6 +1324,114 @@ def occ_rans_decode(packed, payload, n):
         raise PcgcError(f'occ_rans_decode: unsound payload ({int(host[1])} of {chunks} chunks fail their check: states in [2^31, 2^63), '
                         'exactly W_k words consumed, every lane back at 2^31)')
     return mask, int(host[0])
+
+
+def occ_rans_batch_layout(rows_per_frame, chunk_steps):
+    """How a batch's frames are cut into chunks and where their payloads stand in one device buffer (pure host).  rows_per_frame: 1 to 16 row
+    counts; chunk_steps: steps per chunk for every frame (0: each frame is one chunk with its own S_f = max(1, ceil(rows_f / 64))), or one
+    value per frame -> {steps [B] int32, chunks [B], first_chunk [B + 1], row [B + 1], room [B] (8 + 516 K_f + 4 rows_f: a frame without rows
+    has its 8-byte head), pay [B + 1] (byte offsets, multiples of 8)}, int64 but for steps.  Chunks never straddle frames.  ValueError on
+    0 or more than 16 frames, a negative row count or steps outside 0 .. 2^24."""
+    rows = _frame_rows(rows_per_frame, 'occ_rans_batch_layout')
+    want = np.asarray(chunk_steps, dtype=np.int64)
+    if want.ndim > 1 or (want.ndim == 1 and want.size != rows.size) or (want < 0).any() or (want > RANS_MAX_STEPS).any():
+        raise ValueError(f'occ_rans_batch_layout: steps per chunk {want.tolist()} for {rows.size} frames (one value or one per frame, 0 .. 2^24)')
+    want = np.broadcast_to(want, rows.shape)
+    steps = np.where(want > 0, want, np.maximum(1, -(-rows // RANS_LANES)))
+    if (steps > RANS_MAX_STEPS).any():
+        raise ValueError(f'occ_rans_batch_layout: one chunk per frame needs {int(steps.max())} steps (at most 2^24)')
+    chunks = -(-rows // (RANS_LANES * steps))
+    room = 8 + 516 * chunks + 4 * rows
+    edge = lambda v: np.concatenate([[0], np.cumsum(v)]).astype(np.int64)
+    return {'steps': steps.astype(np.int32), 'chunks': chunks, 'first_chunk': edge(chunks), 'row': edge(rows), 'room': room,
+            'pay': edge((room + 7) // 8 * 8)}
+
+
+def _rans_batch_ws(n, chunks, dev):
+    nbytes = int(lib().pcgc_occ_rans_batch_workspace_bytes(n, chunks))
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev), nbytes
+
+
+def occ_rans_payloads(pending):
+    """pending: what occ_rans_encode_batch(.., fetch=False) returned, of one or several calls -> per call the list of its frames' payloads
+    (bytes), all brought down in ONE copy."""
+    parts = [raw[int(pay[f]):int(pay[f]) + int(size[f])] for raw, pay, size in pending for f in range(len(size))]
+    down = torch.cat(parts).cpu().numpy().tobytes()
+    out, at = [], 0
+    for _, _, size in pending:
+        out.append([])
+        for f in range(len(size)):
+            out[-1].append(down[at:at + int(size[f])])
+            at += int(size[f])
+    return out
+
+
+def occ_rans_encode_batch(packed, rows_per_frame, chunk_steps, sums=None, fetch=True):
+    """packed int16 [n] as occ_symbols_segments returns it, frame f the next rows_per_frame[f] rows -> B payloads (bytes), every one what
+    occ_rans_encode gives for that frame alone at its own steps per chunk (occ_rans_batch_layout).  ONE launch sequence and one small
+    synchronising copy for the batch; fetch=False leaves the finished payloads on the device and returns (buffer, offsets, lengths) for
+    occ_rans_payloads to bring down later.  With sums (occ_symbols_segments' int64 [B, 2]) the small copy brings them along:
+    -> (payloads, occupied rows per frame, ideal code length per frame in 2^-16 bit)."""
+    lay = occ_rans_batch_layout(rows_per_frame, chunk_steps)
+    B, n, dev = lay['steps'].size, int(lay['row'][-1]), packed.device
+    if _dev(packed, torch.int16, 'occ_rans_encode_batch: packed').dim() != 1 or packed.shape[0] != n:
+        raise PcgcError(f'occ_rans_encode_batch: packed {tuple(packed.shape)} for {B} frames of {n} rows in all')
+    if sums is not None and tuple(_dev(sums, torch.int64, 'occ_rans_encode_batch: sums').shape) != (B, 2):
+        raise PcgcError(f'occ_rans_encode_batch: sums is occ_symbols_segments\' int64 [{B}, 2]')
+    pay = lay['pay']
+    out = torch.empty(int(pay[-1]) // 8, dtype=torch.int64, device=dev)
+    ws, ws_bytes = _rans_batch_ws(n, int(lay['first_chunk'][-1]), dev)
+    host = np.zeros(3 * B, dtype=np.int64)
+    check(lib().pcgc_occ_rans_encode_batch(_p(packed), B, lay['row'].ctypes.data, lay['steps'].ctypes.data, _p(sums), _p(out), pay.ctypes.data,
+                                           host.ctypes.data, _p(ws), ws_bytes, _stream(packed)), 'occ_rans_encode_batch')
+    pending = (out.view(torch.uint8), pay, host[:B].copy())
+    payloads = occ_rans_payloads([pending])[0] if fetch else pending
+    return payloads if sums is None else (payloads, host[B:2 * B].copy(), host[2 * B:].copy())
+
+
+def occ_rans_decode_batch(packed, rows_per_frame, payloads, mask=None, names=None):
+    """packed int16 [n]: the contexts of a batch's level (occ_symbols_segments without truth), frame f the next rows_per_frame[f] rows;
+    payloads: per frame the bytes of a version-2 payload, or None for a frame that is not decoded here (its slice of the mask keeps what it
+    holds) -> (uint8 mask [n] on the device, occupied rows per frame).  Every payload's S, K and lengths are checked through occ_rans_layout
+    before any launch; one upload, ONE launch sequence and one small copy for the batch.  mask: the uint8 [n] device tensor to write into.
+    PcgcError naming the frame (names[f], else 'frame f') of a bad head or an unsound chunk."""
+    rows = _frame_rows(rows_per_frame, 'occ_rans_decode_batch')
+    B, n, dev = rows.size, int(rows.sum()), packed.device
+    if len(payloads) != B:
+        raise ValueError(f'occ_rans_decode_batch: {len(payloads)} payloads for {B} frames')
+    if _dev(packed, torch.int16, 'occ_rans_decode_batch: packed').dim() != 1 or packed.shape[0] != n:
+        raise PcgcError(f'occ_rans_decode_batch: packed {tuple(packed.shape)} for {B} frames of {n} rows in all')
+    names = [f'frame {f}' for f in range(B)] if names is None else list(names)
+    steps, chunks, pay, size, blob = np.zeros(B, np.int32), np.zeros(B, np.int64), np.zeros(B, np.int64), np.zeros(B, np.int64), bytearray()
+    for f, payload in enumerate(payloads):
+        if payload is None:
+            continue
+        try:
+            steps[f], chunks[f] = occ_rans_layout(payload, int(rows[f]))
+        except PcgcError as e:
+            raise PcgcError(f'{names[f]}: {e}') from None
+        pay[f], size[f] = len(blob), len(payload)
+        blob += bytes(payload) + bytes(-len(payload) % 8)
+    if mask is None:
+        mask = torch.empty(n, dtype=torch.uint8, device=dev)
+    elif tuple(_dev(mask, torch.uint8, 'occ_rans_decode_batch: mask').shape) != (n,):
+        raise PcgcError(f'occ_rans_decode_batch: a mask of {tuple(mask.shape)} for {n} rows')
+    occupied = np.zeros(B, np.int64)
+    if not steps.any():
+        return mask, occupied
+    up = torch.frombuffer(blob, dtype=torch.int64).to(dev)                         # (8-byte aligned on the device)
+    K = int(chunks.sum())
+    ws_bytes = 3 * OCC_MAX_FRAMES * 8 + (K + 1) // 2 * 8                           # (the slot + K offsets; no scratch on this side)
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    row = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+    host = np.zeros(2 * B, dtype=np.int64)
+    check(lib().pcgc_occ_rans_decode_batch(_p(packed), B, row.ctypes.data, steps.ctypes.data, _p(up), pay.ctypes.data, size.ctypes.data, _p(mask),
+                                           host.ctypes.data, _p(ws), ws_bytes, _stream(packed)), 'occ_rans_decode_batch')
+    for f in range(B):
+        if host[B + f]:
+            raise PcgcError(f'{names[f]}: occ_rans_decode_batch: unsound payload ({int(host[B + f])} of {int(chunks[f])} chunks fail their check: '
+                            'states in [2^31, 2^63), exactly W_k words consumed, every lane back at 2^31)')
+    return mask, host[:B].copy()
 
 
 # ------------------------------------------------------------------------------------------------ backward pass (csrc/grad.hip)

@@ -7,7 +7,9 @@ the gap between the ideal length and loss.get_bce on the same forward point.  Bo
 range coder (version 1) and rANS on the device (version 2, phases k_occ_rans_encode / k_occ_rans_decode) in chunks of 64 x --chunk_steps rows;
 --occupancy_coder says which of the two fills the top-level figures (and the --trace run), the other is reported under `other_coder`.
 With --trace it re-runs itself once under `rocprofv3 --kernel-trace --stats` (a fresh child process) and prints the k_occ_* rows.
-    tools/lossless_time.py [--cloud NAME] [--repeat K] [--occupancy_coder {host,device}] [--chunk_steps S[,S..]] [--trace]"""
+With --batch B it does one thing instead: encode_batch + decode_batch of B translated copies of the cloud against B frame-by-frame calls,
+both coders, per phase and per whole call, with bits per file and the byte / voxel equality.
+    tools/lossless_time.py [--cloud NAME] [--repeat K] [--occupancy_coder {host,device}] [--chunk_steps S[,S..]] [--trace] [--batch B]"""
 import argparse, csv, glob, json, os, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -18,6 +20,8 @@ ap.add_argument('--repeat', type=int, default=7)
 ap.add_argument('--occupancy_coder', choices=('host', 'device'), default='device')
 ap.add_argument('--chunk_steps', default='', help='S of the device coder (0: one chunk per level); a comma-separated list adds a table of '
                 'medians and sizes over these values; default: lossless.CHUNK_STEPS')
+ap.add_argument('--batch', type=int, default=0, help='B: one encode_batch + decode_batch of B translated copies of the cloud against B frame-by-frame calls '
+                'in this process, both coders: ms per phase and per whole call, bits per file, same bytes / same voxels (nothing else is run)')
 ap.add_argument('--trace', action='store_true', help='also one rocprofv3 --kernel-trace --stats run of two encode + decode pairs (child process)')
 ap.add_argument('--one-call', action='store_true', help=argparse.SUPPRESS)
 args = ap.parse_args()
@@ -86,6 +90,44 @@ def phases_ms(fn, runs, coder=None):
     coder.times = None
     return {k: round(float(np.median([o.get(k, 0.0) for o in out])) * 1e3, 3) for k in out[0]}
 
+
+def batch_report(B):
+    """B copies of the cloud, each translated by a few voxels (so that levels, contexts and payloads differ), as one collated batch against
+    the same B clouds frame by frame (the single-frame path), in this one process"""
+    runs = max(args.repeat, 5)
+    shifts = [torch.tensor([0, 3 * b, 5 * b, 7 * b], dtype=torch.int32, device=dev) for b in range(B)]
+    singles = [SparseTensor(torch.ones((len(pts), 1), device=dev), coordinates=(coords + s).contiguous(), tensor_stride=1, device=dev) for s in shifts]
+    both = torch.cat([torch.cat([torch.full_like(t.C[:, :1], b), t.C[:, 1:]], 1) for b, t in enumerate(singles)]).contiguous()
+    batch = SparseTensor(torch.ones((len(both), 1), device=dev), coordinates=both, tensor_stride=1, device=dev)
+    postfixes = [f'_{b}' for b in range(B)]
+    suffixes = ('_C.bin', '_F.bin', '_H.bin', '_num_points.bin', lossless.SUFFIX)
+    out = {'cloud': args.cloud, 'points_per_frame': len(pts), 'frames': B, 'runs': runs, 'chunk_steps': coders['device'].chunk_steps,
+           'weights': 'synthetic (the rate says nothing about trained models)'}
+    for name in ('host', 'device'):
+        kw = dict(occupancy_coder=name, chunk_steps=steps_list[0])
+        together, alone = lossless.LosslessCoder(model, prefix + '_batch_' + name, **kw), lossless.LosslessCoder(model, prefix + '_alone_' + name, **kw)
+        enc_alone = lambda: [alone.encode(t, p) for t, p in zip(singles, postfixes)]
+        dec_alone = lambda: [alone.decode(p) for p in postfixes]
+        records, records_alone = together.encode_batch(batch, postfixes), enc_alone()
+        decoded, decoded_alone = together.decode_batch(postfixes), dec_alone()
+        r = {'bits_O_per_file': [rec['bits_O'] for rec in records], 'chunks_per_file': [rec.get('chunks') for rec in records],
+             'candidate_rows_per_file': [rec['rows'] for rec in records],
+             'same_bytes': all(open(together.filename + p + s, 'rb').read() == open(alone.filename + p + s, 'rb').read() for p in postfixes for s in suffixes),
+             'same_records': records == records_alone,
+             'same_voxels': all(lossless.same_voxels(a.C, t.C) and lossless.same_voxels(b.C, t.C) for a, b, t in zip(decoded, decoded_alone, singles)),
+             'median_ms': {'encode_batch': median_ms(lambda: together.encode_batch(batch, postfixes), runs), 'encode_frame_by_frame': median_ms(enc_alone, runs),
+                           'decode_batch': median_ms(lambda: together.decode_batch(postfixes), runs), 'decode_frame_by_frame': median_ms(dec_alone, runs)},
+             'phases_ms_synchronised': {'encode_batch': phases_ms(lambda: together.encode_batch(batch, postfixes), runs, together),
+                                        'encode_frame_by_frame': phases_ms(enc_alone, runs, alone),
+                                        'decode_batch': phases_ms(lambda: together.decode_batch(postfixes), runs, together),
+                                        'decode_frame_by_frame': phases_ms(dec_alone, runs, alone)}}
+        out[name] = r
+    return out
+
+
+if args.batch:
+    print(json.dumps(batch_report(args.batch), indent=1))
+    raise SystemExit(0)
 
 runs = max(args.repeat, 5)
 record = exact.encode(x)
