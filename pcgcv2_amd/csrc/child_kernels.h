@@ -25,7 +25,9 @@
 //
 // Numerics: per output element the products arrive in ascending cell order = ascending kernel offset k, and inside a cell in
 // ascending input channel (16-channel block, K-step, K index) — the canonical fmaf chain of DESIGN.md §3.  A zero B column
-// or an absent (zero) row adds fma(x, 0, acc) = acc.  Bit-identical to the per-row kernels and the oracle (tests).
+// or an absent (zero) row adds fma(x, 0, acc) = acc for finite x and every acc but -0 (fma(+x, 0, -0) = +0, and 0 x inf = NaN:
+// a non-finite row reaches every child of the parents whose halo holds it).  Bit-identical to the per-row kernels and the oracle on
+// finite values, up to the sign of a zero accumulator (tests/test_value_edges_device.py).
 #pragma once
 #include "pcgc_common.h"
 #include "mfma_util.h"
