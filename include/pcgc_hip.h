@@ -389,8 +389,10 @@ int pcgc_occ_tables(uint16_t* p1, int32_t* cost);
  *      if x < L, x = x << 32 | next word (within a step, words go to the renormalising lanes in ascending lane order).  A chunk is sound
  *      iff every stored state is in [2^31, 2^63), exactly W_k words were consumed and every lane ends at x == L; a word index at or past
  *      W_k reads as 0 and marks the chunk unsound.  The decoder reads nothing outside a chunk's words, whatever the bytes say.
- *      rows < 2^31.  workspace: pcgc_occ_rans_workspace_bytes(n, steps) device bytes, 8-byte aligned (no allocation inside); the decoder
- *      uses its first 32 + 8 ceil(K / 2) bytes only and accepts as little. ---- */
+ *      rows < 2^31.  workspace: pcgc_occ_rans_workspace_bytes(n, steps) = pcgc_occ_rans_batch_workspace_bytes(n, K) device bytes, 8-byte
+ *      aligned (no allocation inside): the single entries are the batch of one on the batch's slot layout.  The decoder uses its first
+ *      384 + 8 ceil(K / 2) bytes only and accepts as little (it accepted 32 + 8 ceil(K / 2) while the single entries had a slot layout of
+ *      their own).  The coder's shared parts are csrc/rans_core.h. ---- */
 size_t pcgc_occ_rans_workspace_bytes(int64_t n, int steps);
 /* packed [dev n] as pcgc_occ_symbols writes it -> payload [dev, 8-byte aligned, capacity >= 8 + 516 K + 4 n bytes] in the layout above;
  * host3 [host 3] = the payload's length in bytes and, when sums (pcgc_occ_symbols' [dev 2]) is given, sums[0] and sums[1]: ONE small

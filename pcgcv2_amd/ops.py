@@ -1263,9 +1263,75 @@ def occ_rans_chunks(n, steps):
     return -(-int(n) // (RANS_LANES * int(steps)))
 
 
-def _rans_ws(n, steps, dev):
-    nbytes = int(lib().pcgc_occ_rans_workspace_bytes(n, steps))
+# What the two device coders share on this side (csrc/rans_core.h).  kind: 'occ' (units are rows; a frame without rows still
+# has its 8-byte head) or 'attr' (units are tokens; a frame without tokens has the empty payload).
+_RANS_UNITS = {'occ': 'rows', 'attr': 'tokens'}
+
+
+def _rans_ws(kind, n, steps, dev):
+    nbytes = int(getattr(lib(), f'pcgc_{kind}_rans_workspace_bytes')(n, steps))
     return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev), nbytes
+
+
+def _rans_batch_ws(kind, n, chunks, dev):
+    nbytes = int(getattr(lib(), f'pcgc_{kind}_rans_batch_workspace_bytes')(n, chunks))
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev), nbytes
+
+
+def _rans_layout(kind, payload, n):
+    """the host's checks of one frame's version-2 payload against its n units and its own size -> (S, K)"""
+    who, units, n = f'{kind}_rans', _RANS_UNITS[kind], int(n)
+    if n == 0 and kind == 'attr':
+        if len(payload):
+            raise PcgcError(f'{who}: a payload of {len(payload)} bytes without {units}')
+        return 0, 0
+    if len(payload) < 8:
+        raise PcgcError(f'{who}: {len(payload)} bytes, shorter than the head')
+    steps, chunks = (int(v) for v in np.frombuffer(payload, '<u4', 2))
+    if not 1 <= steps <= RANS_MAX_STEPS:
+        raise PcgcError(f'{who}: {steps} steps per chunk (1 .. 2^24)')
+    if chunks != occ_rans_chunks(n, steps):
+        raise PcgcError(f'{who}: {chunks} chunks declared; {n} {units} in chunks of 64 x {steps} make {occ_rans_chunks(n, steps)}')
+    if len(payload) < 8 + 516 * chunks:
+        raise PcgcError(f'{who}: {len(payload)} bytes, cut inside the tables of {chunks} chunks')
+    words = int(np.frombuffer(payload, '<u4', chunks, 8 + 512 * chunks).astype(np.int64).sum())
+    if 8 + 516 * chunks + 4 * words != len(payload):
+        raise PcgcError(f'{who}: {len(payload)} bytes, but the chunks declare {words} words in all')
+    return steps, chunks
+
+
+def _rans_batch_layout(kind, counts, want):
+    """counts, want [B] int64 as their caller has checked them: units and steps per chunk asked for per frame (0: the frame is one chunk)
+    -> the dictionary of occ_rans_batch_layout / attr_rans_batch_layout; the frames' first units under 'row' or 'tok'"""
+    some = (counts > 0) | (kind == 'occ')                                          # the frame has a payload at all
+    steps = np.where(some, np.where(want > 0, want, np.maximum(1, -(-counts // RANS_LANES))), 0)
+    chunks = -(-counts // (RANS_LANES * np.maximum(steps, 1)))
+    room = np.where(some, 8 + 516 * chunks + 4 * counts, 0)
+    edge = lambda v: np.concatenate([[0], np.cumsum(v)]).astype(np.int64)
+    return {'steps': steps.astype(np.int32), 'chunks': chunks, 'first_chunk': edge(chunks), 'row' if kind == 'occ' else 'tok': edge(counts),
+            'room': room, 'pay': edge((room + 7) // 8 * 8)}
+
+
+def _rans_decode_blob(kind, payloads, counts, names):
+    """payloads: per frame bytes, or None for a frame that is not decoded here; every one is checked against its frame's units (a PcgcError
+    names the frame) -> (steps int32 [B], chunks, pay, size int64 [B], blob: the payloads one behind the other, each padded to 8 bytes)"""
+    B = len(payloads)
+    steps, chunks, pay, size, blob = np.zeros(B, np.int32), np.zeros(B, np.int64), np.zeros(B, np.int64), np.zeros(B, np.int64), bytearray()
+    for f, payload in enumerate(payloads):
+        if payload is None:
+            continue
+        try:
+            steps[f], chunks[f] = _rans_layout(kind, payload, int(counts[f]))
+        except PcgcError as e:
+            raise PcgcError(f'{names[f]}: {e}') from None
+        pay[f], size[f] = len(blob), len(payload)
+        blob += bytes(payload) + bytes(-len(payload) % 8)
+    return steps, chunks, pay, size, blob
+
+
+def _rans_unsound(who, bad, of=''):
+    return PcgcError(f'{who}: unsound payload ({bad}{of} chunks fail their check: states in [2^31, 2^63), exactly W_k words consumed, '
+                     'every lane back at 2^31)')
 
 
 def occ_rans_encode(packed, steps, sums=None):
@@ -1279,7 +1345,7 @@ def occ_rans_encode(packed, steps, sums=None):
         raise PcgcError('occ_rans_encode: sums is occ_symbols\' int64 [2]')
     cap = 8 + 516 * occ_rans_chunks(n, steps) + 4 * n
     out = torch.empty((cap + 7) // 8, dtype=torch.int64, device=dev)
-    ws, ws_bytes = _rans_ws(n, steps, dev)
+    ws, ws_bytes = _rans_ws('occ', n, steps, dev)
     host = np.zeros(3, dtype=np.int64)
     check(lib().pcgc_occ_rans_encode(_p(packed), n, steps, _p(sums), _p(out), cap, host.ctypes.data, _p(ws), ws_bytes, _stream(packed)), 'occ_rans_encode')
     payload = out.view(torch.uint8)[:int(host[0])].cpu().numpy().tobytes()
@@ -1289,19 +1355,7 @@ def occ_rans_encode(packed, steps, sums=None):
 def occ_rans_layout(payload, n):
     """the host's checks of one level's payload of `_O.bin` version 2 against its n rows and its own size -> (S, K).  PcgcError when S is
     outside 1 .. 2^24, K is not ceil(n / (64 S)), the tables do not fit or the word counts do not add up to the byte length."""
-    if len(payload) < 8:
-        raise PcgcError(f'occ_rans: {len(payload)} bytes, shorter than the head')
-    steps, chunks = (int(v) for v in np.frombuffer(payload, '<u4', 2))
-    if not 1 <= steps <= RANS_MAX_STEPS:
-        raise PcgcError(f'occ_rans: {steps} steps per chunk (1 .. 2^24)')
-    if chunks != occ_rans_chunks(n, steps):
-        raise PcgcError(f'occ_rans: {chunks} chunks declared; {n} rows in chunks of 64 x {steps} make {occ_rans_chunks(n, steps)}')
-    if len(payload) < 8 + 516 * chunks:
-        raise PcgcError(f'occ_rans: {len(payload)} bytes, cut inside the tables of {chunks} chunks')
-    words = int(np.frombuffer(payload, '<u4', chunks, 8 + 512 * chunks).astype(np.int64).sum())
-    if 8 + 516 * chunks + 4 * words != len(payload):
-        raise PcgcError(f'occ_rans: {len(payload)} bytes, but the chunks declare {words} words in all')
-    return steps, chunks
+    return _rans_layout('occ', payload, n)
 
 
 def occ_rans_decode(packed, payload, n):
@@ -1315,14 +1369,12 @@ def occ_rans_decode(packed, payload, n):
     steps, chunks = occ_rans_layout(payload, n)
     up = torch.frombuffer(bytearray(payload) + bytes(-len(payload) % 8), dtype=torch.int64).to(dev)        # (8-byte aligned on the device)
     mask = torch.empty(n, dtype=torch.uint8, device=dev)
-    ws_bytes = 32 + (chunks + 1) // 2 * 8                                          # (the slot + K offsets; no scratch on this side)
-    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    ws, ws_bytes = _rans_batch_ws('occ', 0, chunks, dev)                           # (the slot + K offsets; no scratch on this side)
     host = np.zeros(2, dtype=np.int64)
     check(lib().pcgc_occ_rans_decode(_p(packed), n, _p(up), len(payload), steps, _p(mask), host.ctypes.data, _p(ws), ws_bytes, _stream(packed)),
           'occ_rans_decode')
     if host[1]:
-        raise PcgcError(f'occ_rans_decode: unsound payload ({int(host[1])} of {chunks} chunks fail their check: states in [2^31, 2^63), '
-                        'exactly W_k words consumed, every lane back at 2^31)')
+        raise _rans_unsound('occ_rans_decode', int(host[1]), f' of {chunks}')
     return mask, int(host[0])
 
 
@@ -1336,26 +1388,21 @@ def occ_rans_batch_layout(rows_per_frame, chunk_steps):
     want = np.asarray(chunk_steps, dtype=np.int64)
     if want.ndim > 1 or (want.ndim == 1 and want.size != rows.size) or (want < 0).any() or (want > RANS_MAX_STEPS).any():
         raise ValueError(f'occ_rans_batch_layout: steps per chunk {want.tolist()} for {rows.size} frames (one value or one per frame, 0 .. 2^24)')
-    want = np.broadcast_to(want, rows.shape)
-    steps = np.where(want > 0, want, np.maximum(1, -(-rows // RANS_LANES)))
-    if (steps > RANS_MAX_STEPS).any():
-        raise ValueError(f'occ_rans_batch_layout: one chunk per frame needs {int(steps.max())} steps (at most 2^24)')
-    chunks = -(-rows // (RANS_LANES * steps))
-    room = 8 + 516 * chunks + 4 * rows
-    edge = lambda v: np.concatenate([[0], np.cumsum(v)]).astype(np.int64)
-    return {'steps': steps.astype(np.int32), 'chunks': chunks, 'first_chunk': edge(chunks), 'row': edge(rows), 'room': room,
-            'pay': edge((room + 7) // 8 * 8)}
-
-
-def _rans_batch_ws(n, chunks, dev):
-    nbytes = int(lib().pcgc_occ_rans_batch_workspace_bytes(n, chunks))
-    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev), nbytes
+    lay = _rans_batch_layout('occ', rows, np.broadcast_to(want, rows.shape))
+    if (lay['steps'] > RANS_MAX_STEPS).any():
+        raise ValueError(f'occ_rans_batch_layout: one chunk per frame needs {int(lay["steps"].max())} steps (at most 2^24)')
+    return lay
 
 
 def occ_rans_payloads(pending):
     """pending: what occ_rans_encode_batch(.., fetch=False) returned, of one or several calls -> per call the list of its frames' payloads
     (bytes), all brought down in ONE copy."""
-    parts = [raw[int(pay[f]):int(pay[f]) + int(size[f])] for raw, pay, size in pending for f in range(len(size))]
+    return _rans_fetch(pending)
+
+
+def _rans_fetch(pending):
+    """pending: per call (the payload buffer as uint8 on the device, the frames' byte offsets, their lengths) -> per call its frames' bytes"""
+    parts =[raw[int(pay[f]):int(pay[f]) + int(size[f])] for raw, pay, size in pending for f in range(len(size))]
     down = torch.cat(parts).cpu().numpy().tobytes()
     out, at = [], 0
     for _, _, size in pending:
@@ -1380,7 +1427,7 @@ def occ_rans_encode_batch(packed, rows_per_frame, chunk_steps, sums=None, fetch=
         raise PcgcError(f'occ_rans_encode_batch: sums is occ_symbols_segments\' int64 [{B}, 2]')
     pay = lay['pay']
     out = torch.empty(int(pay[-1]) // 8, dtype=torch.int64, device=dev)
-    ws, ws_bytes = _rans_batch_ws(n, int(lay['first_chunk'][-1]), dev)
+    ws, ws_bytes = _rans_batch_ws('occ', n, int(lay['first_chunk'][-1]), dev)
     host = np.zeros(3 * B, dtype=np.int64)
     check(lib().pcgc_occ_rans_encode_batch(_p(packed), B, lay['row'].ctypes.data, lay['steps'].ctypes.data, _p(sums), _p(out), pay.ctypes.data,
                                            host.ctypes.data, _p(ws), ws_bytes, _stream(packed)), 'occ_rans_encode_batch')
@@ -1402,16 +1449,7 @@ def occ_rans_decode_batch(packed, rows_per_frame, payloads, mask=None, names=Non
     if _dev(packed, torch.int16, 'occ_rans_decode_batch: packed').dim() != 1 or packed.shape[0] != n:
         raise PcgcError(f'occ_rans_decode_batch: packed {tuple(packed.shape)} for {B} frames of {n} rows in all')
     names = [f'frame {f}' for f in range(B)] if names is None else list(names)
-    steps, chunks, pay, size, blob = np.zeros(B, np.int32), np.zeros(B, np.int64), np.zeros(B, np.int64), np.zeros(B, np.int64), bytearray()
-    for f, payload in enumerate(payloads):
-        if payload is None:
-            continue
-        try:
-            steps[f], chunks[f] = occ_rans_layout(payload, int(rows[f]))
-        except PcgcError as e:
-            raise PcgcError(f'{names[f]}: {e}') from None
-        pay[f], size[f] = len(blob), len(payload)
-        blob += bytes(payload) + bytes(-len(payload) % 8)
+    steps, chunks, pay, size, blob = _rans_decode_blob('occ', payloads, rows, names)
     if mask is None:
         mask = torch.empty(n, dtype=torch.uint8, device=dev)
     elif tuple(_dev(mask, torch.uint8, 'occ_rans_decode_batch: mask').shape) != (n,):
@@ -1420,17 +1458,14 @@ def occ_rans_decode_batch(packed, rows_per_frame, payloads, mask=None, names=Non
     if not steps.any():
         return mask, occupied
     up = torch.frombuffer(blob, dtype=torch.int64).to(dev)                         # (8-byte aligned on the device)
-    K = int(chunks.sum())
-    ws_bytes = 3 * OCC_MAX_FRAMES * 8 + (K + 1) // 2 * 8                           # (the slot + K offsets; no scratch on this side)
-    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+    ws, ws_bytes = _rans_batch_ws('occ', 0, int(chunks.sum()), dev)                # (the slot + K offsets; no scratch on this side)
     row = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
     host = np.zeros(2 * B, dtype=np.int64)
     check(lib().pcgc_occ_rans_decode_batch(_p(packed), B, row.ctypes.data, steps.ctypes.data, _p(up), pay.ctypes.data, size.ctypes.data, _p(mask),
                                            host.ctypes.data, _p(ws), ws_bytes, _stream(packed)), 'occ_rans_decode_batch')
     for f in range(B):
         if host[B + f]:
-            raise PcgcError(f'{names[f]}: occ_rans_decode_batch: unsound payload ({int(host[B + f])} of {int(chunks[f])} chunks fail their check: '
-                            'states in [2^31, 2^63), exactly W_k words consumed, every lane back at 2^31)')
+            raise _rans_unsound(f'{names[f]}: occ_rans_decode_batch', int(host[B + f]), f' of {int(chunks[f])}')
     return mask, host[:B].copy()
 
 
@@ -2113,8 +2148,7 @@ def attr_rans_encode(table, ctx, tokens, steps):
         return b''
     cap = 8 + 516 * attr_rans_chunks(n, steps) + 4 * n
     out = torch.empty((cap + 7) // 8, dtype=torch.int64, device=dev)
-    nbytes = int(lib().pcgc_attr_rans_workspace_bytes(n, steps))
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    ws, nbytes = _rans_ws('attr', n, steps, dev)
     host = np.zeros(2, dtype=np.int64)
     check(lib().pcgc_attr_rans_encode(_p(table), _p(ctx), _p(tokens), n, steps, _p(out), cap, host.ctypes.data, _p(ws), nbytes, _stream(tokens)),
           'attr_rans_encode')
@@ -2128,24 +2162,7 @@ def attr_rans_layout(payload, n):
     """the host's checks of the payload of `_A.bin` version 2 against its n tokens and its own size -> (S, K).  PcgcError when S is outside
     1 .. 2^24, K is not ceil(n / (64 S)), the tables do not fit or the word counts do not add up to the byte length; n = 0 takes the empty
     payload alone -> (0, 0)."""
-    n = int(n)
-    if n == 0:
-        if len(payload):
-            raise PcgcError(f'attr_rans: a payload of {len(payload)} bytes without tokens')
-        return 0, 0
-    if len(payload) < 8:
-        raise PcgcError(f'attr_rans: {len(payload)} bytes, shorter than the head')
-    steps, chunks = (int(v) for v in np.frombuffer(payload, '<u4', 2))
-    if not 1 <= steps <= RANS_MAX_STEPS:
-        raise PcgcError(f'attr_rans: {steps} steps per chunk (1 .. 2^24)')
-    if chunks != attr_rans_chunks(n, steps):
-        raise PcgcError(f'attr_rans: {chunks} chunks declared; {n} tokens in chunks of 64 x {steps} make {attr_rans_chunks(n, steps)}')
-    if len(payload) < 8 + 516 * chunks:
-        raise PcgcError(f'attr_rans: {len(payload)} bytes, cut inside the tables of {chunks} chunks')
-    words = int(np.frombuffer(payload, '<u4', chunks, 8 + 512 * chunks).astype(np.int64).sum())
-    if 8 + 516 * chunks + 4 * words != len(payload):
-        raise PcgcError(f'attr_rans: {len(payload)} bytes, but the chunks declare {words} words in all')
-    return steps, chunks
+    return _rans_layout('attr', payload, n)
 
 
 def attr_rans_decode(table, tree, payload, n):
@@ -2163,14 +2180,12 @@ def attr_rans_decode(table, tree, payload, n):
         return torch.empty(0, dtype=torch.int16, device=dev), 0
     up = torch.frombuffer(bytearray(payload) + bytes(-len(payload) % 8), dtype=torch.int64).to(dev)        # (8-byte aligned on the device)
     tokens = torch.empty(n, dtype=torch.int16, device=dev)
-    nbytes = int(lib().pcgc_attr_rans_workspace_bytes(n, steps))
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    ws, nbytes = _rans_ws('attr', n, steps, dev)
     host = np.zeros(2, dtype=np.int64)
     check(lib().pcgc_attr_rans_decode(_p(table), _p(tree.offsets), n, _p(up), len(payload), steps, _p(tokens), host.ctypes.data, _p(ws), nbytes,
                                       _stream(tokens)), 'attr_rans_decode')
     if host[1]:
-        raise PcgcError(f'attr_rans_decode: unsound payload ({int(host[1])} of {chunks} chunks fail their check: states in [2^31, 2^63), '
-                        'exactly W_k words consumed, every lane back at 2^31)')
+        raise _rans_unsound('attr_rans_decode', int(host[1]), f' of {chunks}')
     return tokens, int(host[0])
 
 
@@ -2183,12 +2198,7 @@ def attr_rans_batch_layout(tokens_per_frame, chunk_steps):
     want = np.broadcast_to(np.asarray(chunk_steps, dtype=np.int64), counts.shape)
     if (counts < 0).any() or (want < 0).any() or (want > RANS_MAX_STEPS).any():
         raise ValueError(f'attr_rans_batch_layout: token counts {counts.tolist()}, steps per chunk {want.tolist()} (0 .. 2^24)')
-    steps = np.where(counts > 0, np.where(want > 0, want, -(-counts // RANS_LANES)), 0)
-    chunks = np.where(counts > 0, -(-counts // (RANS_LANES * np.maximum(steps, 1))), 0)
-    room = np.where(counts > 0, 8 + 516 * chunks + 4 * counts, 0)
-    edge = lambda v: np.concatenate([[0], np.cumsum(v)]).astype(np.int64)
-    return {'steps': steps.astype(np.int32), 'chunks': chunks, 'first_chunk': edge(chunks), 'tok': edge(counts), 'room': room,
-            'pay': edge((room + 7) // 8 * 8)}
+    return _rans_batch_layout('attr', counts, want)
 
 
 def _attr_tables(tables, frames, dev):
@@ -2214,8 +2224,7 @@ def attr_rans_encode_batch(tables, ctx, tokens, tok, chunk_steps):
         return [b''] * B
     pay, K = lay['pay'], int(lay['first_chunk'][-1])
     out = torch.empty(int(pay[-1]) // 8, dtype=torch.int64, device=dev)
-    nbytes = int(lib().pcgc_attr_rans_batch_workspace_bytes(n, K))
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    ws, nbytes = _rans_batch_ws('attr', n, K, dev)
     host = np.zeros(2 * B, dtype=np.int64)
     check(lib().pcgc_attr_rans_encode_batch(_p(tables), _p(ctx), _p(tokens), B, tok.ctypes.data, lay['steps'].ctypes.data, _p(out), pay.ctypes.data,
                                             host.ctypes.data, _p(ws), nbytes, _stream(tokens)), 'attr_rans_encode_batch')
@@ -2223,10 +2232,7 @@ def attr_rans_encode_batch(tables, ctx, tokens, tok, chunk_steps):
         if host[B + b]:
             raise PcgcError(f'attr_rans_encode_batch: frame {b}: {int(host[B + b])} tokens cannot be coded (outside 0 .. 63, under a context '
                             'outside 0 .. 47, or of frequency 0 in their row)')
-    raw = out.view(torch.uint8)
-    down = torch.cat([raw[int(pay[b]):int(pay[b]) + int(host[b])] for b in range(B)]).cpu().numpy().tobytes()      # the finished payloads, one copy
-    edge = np.concatenate([[0], np.cumsum(host[:B])])
-    return [down[int(edge[b]):int(edge[b + 1])] for b in range(B)]
+    return _rans_fetch([(out.view(torch.uint8), pay, host[:B])])[0]                # the finished payloads, one copy
 
 
 def attr_rans_decode_batch(tables, tree, payloads, tokens=None, names=None):
@@ -2239,16 +2245,7 @@ def attr_rans_decode_batch(tables, tree, payloads, tokens=None, names=None):
     if len(payloads) != B:
         raise PcgcError(f'attr_rans_decode_batch: {len(payloads)} payloads for {B} frames')
     names = [f'frame {b}' for b in range(B)] if names is None else list(names)
-    steps, pay, size, blob = np.zeros(B, np.int32), np.zeros(B, np.int64), np.zeros(B, np.int64), bytearray()
-    for b, payload in enumerate(payloads):
-        if payload is None:
-            continue
-        try:
-            steps[b], _ = attr_rans_layout(payload, int(tok[b + 1] - tok[b]))
-        except PcgcError as e:
-            raise PcgcError(f'{names[b]}: {e}') from None
-        pay[b], size[b] = len(blob), len(payload)
-        blob += bytes(payload) + bytes(-len(payload) % 8)
+    steps, chunks, pay, size, blob = _rans_decode_blob('attr', payloads, np.diff(tok), names)
     tables = _attr_tables(tables, B, dev)
     n = int(tok[-1])
     if tokens is None:
@@ -2258,18 +2255,15 @@ def attr_rans_decode_batch(tables, tree, payloads, tokens=None, names=None):
     escapes = np.zeros(B, np.int64)
     if not steps.any():
         return tokens, escapes
-    K = int(sum(attr_rans_chunks(tok[b + 1] - tok[b], steps[b]) for b in range(B) if steps[b]))
     up = torch.frombuffer(blob, dtype=torch.int64).to(dev)
-    nbytes = int(lib().pcgc_attr_rans_batch_workspace_bytes(n, K))
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    ws, nbytes = _rans_batch_ws('attr', n, int(chunks.sum()), dev)
     host = np.zeros(2 * B, dtype=np.int64)
     check(lib().pcgc_attr_rans_decode_batch(_p(tables), _p(tree.offsets), B, tok.ctypes.data, steps.ctypes.data, _p(up), pay.ctypes.data,
                                             size.ctypes.data, _p(tokens), host.ctypes.data, _p(ws), nbytes, _stream(tokens)),
           'attr_rans_decode_batch')
     for b in range(B):
         if host[B + b]:
-            raise PcgcError(f'{names[b]}: attr_rans_decode_batch: unsound payload ({int(host[B + b])} chunks fail their check: states in '
-                            '[2^31, 2^63), exactly W_k words consumed, every lane back at 2^31)')
+            raise _rans_unsound(f'{names[b]}: attr_rans_decode_batch', int(host[B + b]))
     return tokens, host[:B].copy()
 
 

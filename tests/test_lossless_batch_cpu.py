@@ -107,3 +107,13 @@ def test_native_entries_refuse_before_anything_is_touched():
     assert L.pcgc_occ_symbols_segments(None, 1, 2, np.array([8, -8], np.int64).ctypes.data, None, None, None, None) == -2
     assert L.pcgc_occ_symbols_segments(None, 0, 1, one.ctypes.data, None, None, None, None) == -2
     assert L.pcgc_occ_rans_batch_workspace_bytes(128, 3) == 3 * 16 * 8 + 16 + 4 * 128 + 64
+
+
+@pytest.mark.parametrize('kind', ['occ', 'attr'])
+def test_the_single_sizing_entry_is_the_batch_entry_at_the_frame_s_own_chunks(kind):
+    """the single entries run on the batch's slot layout (csrc/rans_core.h): one workspace layout per coder"""
+    L = ops.lib()
+    single, batch = getattr(L, f'pcgc_{kind}_rans_workspace_bytes'), getattr(L, f'pcgc_{kind}_rans_batch_workspace_bytes')
+    for n in (0, 1, 64, 65, 193):
+        for S in (1, 3):
+            assert int(single(n, S)) == int(batch(n, -(-n // (64 * S)))), (kind, n, S)

@@ -12,10 +12,12 @@ pytestmark = pytest.mark.gpu
 
 import lossless_reference as lr
 import rans_reference as rr
+import scratch_arena as SA
 from pcgcv2_amd import lossless, ops, synthetic
 from pcgcv2_amd.coder import STREAMS
 from pcgcv2_amd.pcc_model import PCCModel
 from pcgcv2_amd.sparse import SparseTensor, sparse_collate
+from scratch_arena import Arena
 
 DEV = torch.device('cuda:0')
 HEAD = struct.Struct('<4sII6Q')
@@ -106,6 +108,58 @@ def test_unsound_payloads_are_refused_and_the_sound_one_still_decodes():
             pytest.fail(f'{what}: decoded')
     mask, occupied = ops.occ_rans_decode(contexts, good, len(ctx))
     assert np.array_equal(mask.cpu().numpy(), bit) and occupied == int(bit.sum())
+
+
+# ---- the single entries on the batch's slot layout (csrc/rans_core.h) ---------------------------------------------------------------------------
+def test_single_decoder_takes_exactly_the_batch_slot_and_refuses_one_byte_less():
+    """pcgc_occ_rans_decode at n = 65, S = 1 (two chunks) needs 384 + 8 ceil(K / 2) bytes: a byte less is refused before any launch (the mask
+    and the workspace under guard bands stay unwritten), exactly as much decodes what the definition says"""
+    n, S = 65, 1
+    ctx, bit = rr.model_drawn(n, seed=5)
+    payload = rr.encode(ctx, bit, S)
+    need = 384 + 8 * ((rr.chunks_of(n, S) + 1) // 2)
+    assert rr.chunks_of(n, S) == 2 and need == 392
+    arena = Arena()
+    with SA.installed(arena):
+        ws = ops.torch.empty(need, dtype=torch.uint8, device=DEV)
+        mask = ops.torch.empty(n, dtype=torch.uint8, device=DEV)
+    contexts = _packed(ctx)
+    up = torch.frombuffer(bytearray(payload + bytes(-len(payload) % 8)), dtype=torch.uint8).to(DEV)
+    host = np.zeros(2, np.int64)
+    stream = torch.cuda.current_stream(DEV).cuda_stream
+    dec = lambda ws_bytes: ops.lib().pcgc_occ_rans_decode(contexts.data_ptr(), n, up.data_ptr(), len(payload), S, mask.data_ptr(), host.ctypes.data,
+                                                          ws.data_ptr(), ws_bytes, stream)
+    assert dec(need - 1) == -2 and 'too small' in ops.lib().pcgc_last_error().decode()
+    arena.check()
+    assert not any(b.payload().any() for b in arena.blocks), 'a refused call wrote to its buffers'
+    assert dec(need) == 0 and host.tolist() == [int(bit.sum()), 0]
+    assert np.array_equal(mask.cpu().numpy(), rr.decode(ctx, payload)) and np.array_equal(mask.cpu().numpy(), bit)
+    arena.check()
+
+
+def test_encoder_zeroes_its_slot_on_a_workspace_full_of_ones():
+    """frames of (64, 0, 64) rows on recycled scratch whose workspace block arrives as 0xff bytes: the payloads are the definition's"""
+    S, split = 1, (64, 0, 64)
+    frames = [rr.model_drawn(n, seed=7 + f) for f, n in enumerate(split)]
+    ctx, bit = np.concatenate([c for c, _ in frames]), np.concatenate([b for _, b in frames])
+    want = [rr.encode(c, b, S) for c, b in frames]
+
+    def run(arena):
+        with SA.installed(arena):
+            out = ops.occ_rans_encode_batch(_packed(ctx, bit), split, S)
+        arena.finish()
+        arena.check()
+        return out
+
+    rec = Arena()
+    assert run(rec) == want
+    workspace = [b for b in rec.blocks if b.caller == '_rans_batch_ws']
+    assert len(workspace) == 1
+    workspace[0].payload().view(torch.uint8).fill_(0xff)
+    stale = rec.replay()
+    assert run(stale) == want
+    allocs, replayed, _ = stale.stats()
+    assert replayed == allocs and not stale.served_fresh
 
 
 # ---- LosslessCoder(occupancy_coder='device') ------------------------------------------------------------------------------------------------

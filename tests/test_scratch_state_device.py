@@ -506,7 +506,7 @@ def _rans_cases():
 @pytest.mark.parametrize('name, S, a, b', _rans_cases(), ids=[c[0].replace(' ', '_') for c in _rans_cases()])
 def test_occ_rans_encode_and_decode(name, S, a, b, ops):
     """the payload has exactly its capacity of 8 + 516 K + 4 n bytes (+ up to 7 to the int64 it is allocated in) between its guards, the
-    decoder's workspace exactly the host's 32 + 8 ceil(K / 2)"""
+    decoder's workspace exactly what the library answers for K chunks and no rows"""
     def fn(i):
         ctx, bit = i
         payload = ops.occ_rans_encode(_packed(ctx, bit), S)
