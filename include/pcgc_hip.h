@@ -869,6 +869,38 @@ typedef struct pcgc_collate_item {
 int pcgc_collate_rows(const uint8_t* arena /*[dev] 16-byte aligned*/, const pcgc_collate_item* items /*[host n_items]*/, int n_items,
                       int32_t* coords_out /*[dev N,4] 16-byte aligned*/, float* feats_out /*[dev N,1]*/, void* stream);
 
+/* ---- Voxelising a raw cloud (csrc/voxelize.hip; the definition is tests/voxelize_reference.py): points [n,3], float32
+ *      (is_f64 = 0) or float64 (1) rows in the caller's units, packed, n = 1 .. 2^31 - 1 (anything else is -2 before anything is touched)
+ *      -> the distinct voxels of a `bits`-bit lattice (1 .. 20) in (z, y, x) order, the rows merged into each, one colour per voxel.
+ *      float32 values are widened exactly and take the float64 path from there.  Minima, maxima and integer sums only: every output is
+ *      exact and the same on every run.  Four entries, called in this order; the host decides the frame between the first two and sizes
+ *      the outputs between the last two.  Buffers are the caller's; everything runs on `stream`. ---- */
+/* sorted rows per workgroup of pcgc_voxelize_merge */
+int64_t pcgc_voxelize_tile_rows(void);
+/* bounds [6] (dev, double): the minimum of x, y, z and then the maximum of x, y, z over the rows that hold neither a NaN nor an infinity
+ * (a zero is written as +0; +inf / -inf when there is no such row); bad_rows [1] (dev): the rows that do. */
+int64_t pcgc_voxelize_bounds_workspace_bytes(int64_t n);
+int pcgc_voxelize_bounds(const void* points, int is_f64, int64_t n, double* bounds, int64_t* bad_rows, void* workspace,
+                         size_t workspace_bytes, void* stream);
+/* q[a] = rint((double(p[a]) - origin[a]) * scale): the difference and the product each rounded once to fp64, ties to even.
+ * keys [n] (uint64) = qz << 40 | qy << 20 | qx; rows [n] = 0 .. n - 1; outside [1] (dev): the rows with a q outside [0, 2^bits - 1] or
+ * not a number (their key is 0; the caller refuses the cloud when the count is not 0). */
+int pcgc_voxelize_quantize(const void* points, int is_f64, int64_t n, int bits, double origin_x, double origin_y, double origin_z,
+                           double scale, uint64_t* keys, int32_t* rows, int64_t* outside, void* stream);
+/* (keys, rows) sorted by key, stably: inside a voxel the rows ascend -> sorted_keys [n], sorted_rows [n]; rank [n]: 1 + the output row
+ * of the voxel of sorted row i, so rank[n - 1] is the number of voxels m.  The inputs are left as they are. */
+int64_t pcgc_voxelize_heads_workspace_bytes(int64_t n);
+int pcgc_voxelize_heads(const uint64_t* keys, const int32_t* rows, int64_t n, int bits, uint64_t* sorted_keys, int32_t* sorted_rows,
+                        int32_t* rank, void* workspace, size_t workspace_bytes, void* stream);
+/* coords [m,4] (16-byte aligned): rows (0, x, y, z) ascending in (z, y, x); counts [m]: the input rows of each voxel; voxel_of [n]: the
+ * output row of every input row.  colours [n,3] (uint8) or NULL, colours_out [m,3] or NULL with it: merge_first = 0 the mean per channel,
+ * floor((2 sum + count) / (2 count)) over 64-bit sums; 1 the colour of the voxel's lowest input row.  A run of equal keys is reduced
+ * inside its workgroup; only a run that crosses a multiple of pcgc_voxelize_tile_rows() is added up with (integer) atomics. */
+int64_t pcgc_voxelize_merge_workspace_bytes(int64_t m);
+int pcgc_voxelize_merge(const uint64_t* sorted_keys, const int32_t* sorted_rows, const int32_t* rank, int64_t n, int64_t m,
+                        const uint8_t* colours, int merge_first, int32_t* coords, int32_t* counts, int32_t* voxel_of, uint8_t* colours_out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -197,6 +197,14 @@ SIGNATURES = {
     'pcgc_mesh_voxelize_workspace_bytes': (sz, [i32]),
     'pcgc_mesh_voxelize': (ci, [vp, i64, vp, vp, i64, C.c_uint64, i64, vp, i32, vp, i64, vp, vp, sz, vp]),
     'pcgc_collate_rows': (ci, [vp, vp, ci, vp, vp, vp]),
+    'pcgc_voxelize_tile_rows': (i64, []),
+    'pcgc_voxelize_bounds_workspace_bytes': (i64, [i64]),
+    'pcgc_voxelize_bounds': (ci, [vp, ci, i64, vp, vp, vp, sz, vp]),
+    'pcgc_voxelize_quantize': (ci, [vp, ci, i64, ci, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]),
+    'pcgc_voxelize_heads_workspace_bytes': (i64, [i64]),
+    'pcgc_voxelize_heads': (ci, [vp, vp, i64, ci, vp, vp, vp, vp, sz, vp]),
+    'pcgc_voxelize_merge_workspace_bytes': (i64, [i64]),
+    'pcgc_voxelize_merge': (ci, [vp, vp, vp, i64, i64, vp, ci, vp, vp, vp, vp, vp, sz, vp]),
 }
 
 

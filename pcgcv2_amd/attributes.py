@@ -25,6 +25,7 @@ AttributeCoder.encode_batch / decode_batch code up to 16 frames in one pass over
 
     python -m pcgcv2_amd.attributes --filedir CLOUD.ply [MORE.ply ...] --qstep Q [--qstep_chroma Qc] [--outdir DIR]
                                     [--attribute_coder device [--chunk_steps S]]        (several files: one batch)
+                                    [--voxelize B [--merge mean|first] [--devoxelize]]  (raw clouds: voxelised to B bits first, voxelize.py)
 """
 import os
 import struct
@@ -492,11 +493,28 @@ def main(argv=None):
     p.add_argument("--attribute_coder", choices=sorted(CODERS), default='host',
                    help="host: the payload coded by the host range coder (_A.bin version 1); device: interleaved rANS on the GPU (version 2)")
     p.add_argument("--chunk_steps", type=int, default=CHUNK_STEPS, help="device coder: steps per chunk of 64 lanes (0: one chunk)")
+    p.add_argument("--voxelize", metavar='B', type=int, default=None,
+                   help="the files are raw clouds (float coordinates in any unit, ASCII or binary PLY, several points per voxel): voxelise "
+                        "each to B bits first (voxelize.py; _vox.ply and _V.bin are written), then code _vox.ply")
+    p.add_argument("--merge", choices=('mean', 'first'), default='mean', help="with --voxelize: the colour of a voxel, the mean of its points or its first point")
+    p.add_argument("--devoxelize", action='store_true', help="with --voxelize: also write _dec_units.ply, the decoded cloud in the input's units (by _V.bin)")
     args = p.parse_args(argv)
+    if args.voxelize is not None and not 1 <= args.voxelize <= 20:
+        p.error(f'--voxelize {args.voxelize}: a bit depth in 1 .. 20')
+    if args.devoxelize and args.voxelize is None:
+        p.error('--devoxelize needs --voxelize')
+    raw = []
+    if args.voxelize is not None:                        # every raw cloud becomes its _vox.ply; the flow below takes those files
+        from . import voxelize
+        raw = [voxelize.in_front(f, args.outdir, args.voxelize, args.merge) for f in args.filedir]
+        args.filedir = [vox for vox, _ in raw]
     if len(args.filedir) == 1:
         run(args.filedir[0], args.outdir, args.qstep, args.qstep_chroma, args.attribute_coder, args.chunk_steps)
     else:
         run_batch(args.filedir, args.outdir, args.qstep, args.qstep_chroma, args.attribute_coder, args.chunk_steps)
+    if args.devoxelize:
+        for vox, raw_prefix in raw:
+            voxelize.write_units(raw_prefix, os.path.join(args.outdir, os.path.split(vox)[-1].split('.')[0]) + '_dec.ply')
 
 
 if __name__ == '__main__':

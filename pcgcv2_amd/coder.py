@@ -653,7 +653,16 @@ def _parse_cli(argv):
     p.add_argument("--attribute_coder", choices=('host', 'device'), default='host',
                    help="with --attributes: who codes the payload of _A.bin, the host range coder (version 1) or interleaved rANS on the "
                         "device (version 2)")
+    p.add_argument("--voxelize", metavar='B', type=int, default=None,
+                   help="--filedir is a raw cloud (float coordinates in any unit, ASCII or binary PLY, several points per voxel): voxelise it "
+                        "to B bits first (voxelize.py; _vox.ply and _V.bin are written), then code _vox.ply; --res becomes 2^B")
+    p.add_argument("--merge", choices=('mean', 'first'), default='mean', help="with --voxelize: the colour of a voxel, the mean of its points or its first point")
+    p.add_argument("--devoxelize", action='store_true', help="with --voxelize: also write _dec_units.ply, the decoded cloud in the input's units (by _V.bin)")
     args = p.parse_args(argv)
+    if args.voxelize is not None and not 1 <= args.voxelize <= 20:
+        p.error(f'--voxelize {args.voxelize}: a bit depth in 1 .. 20')
+    if args.devoxelize and args.voxelize is None:
+        p.error('--devoxelize needs --voxelize')
     if args.attributes is not None:
         try:
             q = [int(v) for v in args.attributes.split(',')]
@@ -715,10 +724,17 @@ def _code_attributes(filedir, prefix, x_dec, qsteps, coder='host'):
 
 def main(argv=None):
     args = _parse_cli(argv)
+    raw_prefix = None
+    if args.voxelize is not None:                        # the raw cloud becomes _vox.ply; everything below takes that file as its --filedir
+        from . import voxelize
+        args.filedir, raw_prefix = voxelize.in_front(args.filedir, args.outdir, args.voxelize, args.merge)
+        args.res = 1 << args.voxelize
     if args.lossless:
         from . import lossless
         lossless.run(args.ckptdir, args.filedir, args.outdir, occupancy_coder=args.occupancy_coder, attributes=args.attributes,
                      attribute_coder=args.attribute_coder)
+        if args.devoxelize:
+            voxelize.write_units(raw_prefix, os.path.join(args.outdir, os.path.split(args.filedir)[-1].split('.')[0]) + '_dec.ply')
         return
     if args.attributes is not None and args.scaling_factor != 1:
         raise ValueError('--attributes codes colours on the decoded lattice: it does not combine with --scaling_factor')
@@ -767,6 +783,8 @@ def main(argv=None):
     print('D1 PSNR:\t', metrics["mseF,PSNR (p2point)"][0])
     if args.recolour or args.attributes is not None:
         print('Colour PSNR (Y):\t', colour['c[0],PSNRF'])
+    if args.devoxelize:
+        voxelize.write_units(raw_prefix, prefix + '_dec.ply')
 
 
 if __name__ == '__main__':

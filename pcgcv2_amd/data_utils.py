@@ -101,6 +101,86 @@ def read_ply_ascii_with_colours(path):
     return xyz, np.ascontiguousarray(rgb.astype(np.uint8))
 
 
+_PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2', 'ushort': 'u2', 'uint16': 'u2',
+              'int': 'i4', 'int32': 'i4', 'uint': 'u4', 'uint32': 'u4', 'float': 'f4', 'float32': 'f4', 'double': 'f8', 'float64': 'f8'}
+_PLY_FORMATS = {'ascii': None, 'binary_little_endian': '<', 'binary_big_endian': '>'}
+
+
+def _ply_header(path):
+    """-> (format, elements, header bytes) of a PLY of any format; elements: [(name, count, [(property, type or None for a list)])] in
+    file order.  ValueError for a file that is no PLY, has no end_header or names an unknown format."""
+    fmt, elements, size = None, [], 0
+    with open(path, 'rb') as f:
+        if f.readline().strip() != b'ply':
+            raise ValueError(f'{path}: not a PLY file')
+        f.seek(0)
+        for line in f:
+            size += len(line)
+            t = line.decode('ascii', 'replace').split()
+            if not t:
+                continue
+            if t[0] == 'format' and len(t) >= 2:
+                fmt = t[1]
+            elif t[0] == 'element' and len(t) == 3:
+                elements.append((t[1], int(t[2]), []))
+            elif t[0] == 'property' and elements and len(t) >= 3:
+                elements[-1][2].append((t[-1], None if t[1] == 'list' else t[1]))
+            elif t[0] == 'end_header':
+                break
+        else:
+            raise ValueError(f'{path}: no end_header')
+    if fmt not in _PLY_FORMATS:
+        raise ValueError(f'{path}: format {fmt!r}; one of {sorted(_PLY_FORMATS)}')
+    return fmt, elements, size
+
+
+def _ply_row_dtype(path, element, order):
+    name, _, props = element
+    fields = []
+    for prop, kind in props:
+        if kind is None:
+            raise ValueError(f'{path}: element {name!r} has a list property ({prop!r}) and stands in front of the vertices: '
+                             'its size cannot be known without reading it; write the vertex element first')
+        if kind not in _PLY_TYPES:
+            raise ValueError(f'{path}: property {prop!r} of element {name!r} has the unknown type {kind!r}')
+        fields.append((prop, order + _PLY_TYPES[kind]))
+    if len({p for p, _ in fields}) != len(fields):
+        raise ValueError(f'{path}: element {name!r} names a property twice')
+    return np.dtype(fields)
+
+
+def read_ply_with_colours(path):
+    """A PLY of any format -> (coordinates float64 [n,3], colours uint8 [n,3] or None), as read_ply_ascii_with_colours gives them for an
+    ASCII file.  binary_little_endian and binary_big_endian: the vertex element is read through a numpy structured dtype built from the
+    header (char uchar short ushort int uint float double and their int8 .. float64 names, in any column order); elements behind the
+    vertices are ignored; ValueError for an element with a list property in front of them and for a file that ends inside them."""
+    fmt, elements, at = _ply_header(path)
+    if fmt == 'ascii':
+        return read_ply_ascii_with_colours(path)
+    order = _PLY_FORMATS[fmt]
+    for element in elements:
+        if element[0] == 'vertex':
+            break
+        at += element[1] * _ply_row_dtype(path, element, order).itemsize
+    else:
+        raise ValueError(f'{path}: no vertex element')
+    n, row = element[1], _ply_row_dtype(path, element, order)
+    names = row.names or ()
+    if not all(c in names for c in 'xyz'):
+        raise ValueError(f'{path}: no x / y / z vertex properties')
+    have = os.path.getsize(path) - at
+    if n < 0 or have < n * row.itemsize:
+        raise ValueError(f'{path}: {n} vertices of {row.itemsize} bytes declared, {max(have, 0)} bytes behind the header (cut short)')
+    data = np.fromfile(path, dtype=row, count=n, offset=at)
+    xyz = np.stack([data[c].astype(np.float64) for c in 'xyz'], 1) if n else np.zeros((0, 3), np.float64)
+    if not all(c in names for c in _RGB):
+        return np.ascontiguousarray(xyz), None
+    rgb = np.stack([data[c].astype(np.float64) for c in _RGB], 1) if n else np.zeros((0, 3), np.float64)
+    if rgb.size and (rgb.min() < 0 or rgb.max() > 255 or not np.array_equal(rgb, np.rint(rgb))):
+        raise ValueError(f'{path}: red / green / blue are not 8-bit integers')
+    return np.ascontiguousarray(xyz), np.ascontiguousarray(rgb.astype(np.uint8))
+
+
 def write_ply_ascii_geo_rgb(filedir, coords, rgb):
     """ASCII PLY with `property float x/y/z` and `property uchar red/green/blue`, integer text (native writer): what mpeg-pcc-dmetric's
     `-c 1` and read_ply_ascii_with_colours read; read_ply_ascii_geo reads its coordinates."""

@@ -2447,6 +2447,108 @@ def collate_rows(arena, items, out=None):
     return coords[:n], feats[:n]
 
 
+# ------------------------------------------------------------------------------------------------ voxelising a raw cloud
+VOXELIZE_MERGES = {'mean': 0, 'first': 1}
+VOXELIZE_MAX_ROWS = (1 << 31) - 1
+Voxels = namedtuple('Voxels', 'coords counts voxel_of colours origin scale bits')
+
+
+def voxelize_tile_rows():
+    return int(lib().pcgc_voxelize_tile_rows())
+
+
+def voxelize_frame(lo, hi, bits, origin=None, scale=None):
+    """the frame of tests/voxelize_reference.py from the per-axis minima and maxima (fp64) -> (origin (x, y, z), scale), Python floats.
+    ValueError for an origin that is not finite and a scale that is not finite and positive."""
+    lo, hi = [float(v) for v in lo], [float(v) for v in hi]
+    origin = lo if origin is None else [float(v) for v in origin]
+    if len(origin) != 3:
+        raise ValueError(f'voxelize: origin {origin}: three values')
+    if scale is None:
+        e = max(h - l for h, l in zip(hi, lo))
+        with np.errstate(over='ignore'):
+            scale = float(np.float64((1 << bits) - 1) / np.float64(e)) if e != 0 else 1.0
+    scale = float(scale)
+    if not all(np.isfinite(v) for v in origin):
+        raise ValueError(f'voxelize: origin {origin} is not finite')
+    if not (np.isfinite(scale) and scale > 0):
+        raise ValueError(f'voxelize: scale {scale} is not finite and positive')
+    return tuple(origin), scale
+
+
+def voxelize(points, colours=None, bits=10, origin=None, scale=None, merge='mean', times=None):
+    """points float32 or float64 [N,3] (device) in any units, colours uint8 [N,3] or None -> Voxels: coords int32 [M,4] rows (0, x, y, z)
+    of the distinct voxels in (z, y, x) order, counts int32 [M], voxel_of int32 [N], colours uint8 [M,3] or None, and the frame: origin
+    (x, y, z), scale, bits.  q = rint((float64(p) - origin) * scale); origin and scale default to the minimum and (2^bits - 1) / the largest
+    extent.  merge: 'mean' (rounds a half up) or 'first' (the voxel's lowest input row).  Every output equals tests/voxelize_reference.py.
+    Strided tensors are packed first.  ValueError naming the count for rows with a NaN or an infinity, and for rows the frame given puts
+    outside [0, 2^bits - 1].  N = 0 returns empty outputs without a launch.  times (measurement hook): a dict -> seconds of 'bounds',
+    'quantise', 'sort', 'merge' and 'copies' added to it, with a synchronisation after each."""
+    if not torch.is_tensor(points) or not points.is_cuda:
+        raise PcgcError('voxelize: points must be a ROCm device tensor (no CPU fallback exists)')
+    if points.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f'voxelize: points must be float32 or float64, got {points.dtype}')
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f'voxelize: points must be [N,3], got {tuple(points.shape)}')
+    if isinstance(bits, bool) or not isinstance(bits, (int, np.integer)) or not 1 <= bits <= 20:
+        raise ValueError(f'voxelize: bits {bits!r}: an integer in 1 .. 20')
+    if merge not in VOXELIZE_MERGES:
+        raise ValueError(f'voxelize: merge {merge!r}: one of {sorted(VOXELIZE_MERGES)}')
+    n, dev, bits = points.shape[0], points.device, int(bits)
+    if n > VOXELIZE_MAX_ROWS:
+        raise ValueError(f'voxelize: {n} rows; at most 2^31 - 1')
+    if colours is not None:
+        if not torch.is_tensor(colours) or colours.device != dev or colours.dtype != torch.uint8 or tuple(colours.shape) != (n, 3):
+            raise ValueError(f'voxelize: colours must be uint8 [{n},3] on the device of the points')
+        colours = colours.contiguous()
+    points = points.contiguous()
+    if n == 0:
+        o = (0.0, 0.0, 0.0) if origin is None else tuple(float(v) for v in origin)
+        return Voxels(torch.empty((0, 4), dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
+                      torch.empty(0, dtype=torch.int32, device=dev),
+                      None if colours is None else torch.empty((0, 3), dtype=torch.uint8, device=dev), o, 1.0 if scale is None else float(scale), bits)
+    is_f64 = int(points.dtype == torch.float64)
+    L, s = lib(), _stream(points)
+    with torch.cuda.device(dev):
+        t0 = tick_phase(times, None, 0.0, dev)
+        bounds = torch.empty(6, dtype=torch.float64, device=dev)
+        status = torch.empty(2, dtype=torch.int64, device=dev)              # rows with a NaN or an infinity | rows outside the lattice
+        ws_bytes = max(int(L.pcgc_voxelize_bounds_workspace_bytes(n)), int(L.pcgc_voxelize_heads_workspace_bytes(n)))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        check(L.pcgc_voxelize_bounds(_p(points), is_f64, n, _p(bounds), _p(status), _p(ws), ws_bytes, s), 'voxelize_bounds')
+        t0 = tick_phase(times, 'bounds', t0, dev)
+        bad = int(status[0].item())
+        if bad:
+            raise ValueError(f'voxelize: {bad} of {n} rows hold a NaN or an infinity')
+        b = bounds.cpu().tolist()
+        t0 = tick_phase(times, 'copies', t0, dev)
+        origin, scale = voxelize_frame(b[:3], b[3:], bits, origin, scale)
+        keys = torch.empty(n, dtype=torch.int64, device=dev)
+        rows = torch.empty(n, dtype=torch.int32, device=dev)
+        check(L.pcgc_voxelize_quantize(_p(points), is_f64, n, bits, origin[0], origin[1], origin[2], scale, _p(keys), _p(rows),
+                                       status[1:].data_ptr(), s), 'voxelize_quantize')
+        t0 = tick_phase(times, 'quantise', t0, dev)
+        sorted_keys, sorted_rows, rank = torch.empty_like(keys), torch.empty_like(rows), torch.empty_like(rows)
+        check(L.pcgc_voxelize_heads(_p(keys), _p(rows), n, bits, _p(sorted_keys), _p(sorted_rows), _p(rank), _p(ws), ws_bytes, s), 'voxelize_heads')
+        t0 = tick_phase(times, 'sort', t0, dev)
+        outside, m = torch.stack([status[1], rank[n - 1].to(torch.int64)]).cpu().tolist()
+        t0 = tick_phase(times, 'copies', t0, dev)
+        if outside:
+            raise ValueError(f'voxelize: {outside} of {n} rows fall outside [0, 2^{bits} - 1] in the frame given '
+                             f'(origin {list(origin)}, scale {scale})')
+        del keys, rows
+        coords = torch.empty((m, 4), dtype=torch.int32, device=dev)
+        counts = torch.empty(m, dtype=torch.int32, device=dev)
+        voxel_of = torch.empty(n, dtype=torch.int32, device=dev)
+        out = None if colours is None else torch.empty((m, 3), dtype=torch.uint8, device=dev)
+        ws_bytes = int(L.pcgc_voxelize_merge_workspace_bytes(m))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        check(L.pcgc_voxelize_merge(_p(sorted_keys), _p(sorted_rows), _p(rank), n, m, _p(colours), VOXELIZE_MERGES[merge], _p(coords), _p(counts),
+                                    _p(voxel_of), _p(out), _p(ws), ws_bytes, s), 'voxelize_merge')
+        tick_phase(times, 'merge', t0, dev)
+    return Voxels(coords, counts, voxel_of, out, origin, scale, bits)
+
+
 # ------------------------------------------------------------------------------------------------ host codecs (numpy)
 def _np(a, dt):
     return np.ascontiguousarray(a, dtype=dt)
