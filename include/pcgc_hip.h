@@ -901,6 +901,38 @@ int pcgc_voxelize_merge(const uint64_t* sorted_keys, const int32_t* sorted_rows,
                         const uint8_t* colours, int merge_first, int32_t* coords, int32_t* counts, int32_t* voxel_of, uint8_t* colours_out,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Cleaning a voxelised cloud (csrc/clean.hip; the definition is tests/clean_reference.py): rows are DISTINCT voxels
+ *      (batch, x, y, z) that have passed pcgc_coords_check_order, n = 0 .. 2^24 (anything else, a null pointer or an undersized workspace is
+ *      -2 before anything is touched).  Integers only; every output is a function of the voxel set and the row order.  Buffers are the
+ *      caller's; everything runs on `stream`. ---- */
+/* Stage 1: neighbours [n] (ORIGINAL rows) = the other voxels of the row's batch with |q - p|^2 <= r2 (1 .. 64, never clamped); keep [n] =
+ * neighbours >= min_neighbours; repeated [1] (dev) = the rows that repeat an earlier voxel (the caller refuses the cloud when it is not 0).
+ * The cloud is given by its D2 index as for pcgc_normals_estimate (qs, perm, cell hash, masks, runlen); ball = pcgc_normals_ball_masks(r2). */
+int pcgc_clean_neighbours(const int32_t* qs /*[dev n,4]*/, const int32_t* perm, int64_t n, const uint64_t* cell_keys, const int32_t* cell_vals,
+                          int64_t cell_cap, const uint64_t* masks, const int32_t* runlen, const uint64_t* ball /*[dev]*/, int32_t r2,
+                          int32_t min_neighbours, int32_t* neighbours /*[dev n]*/, uint8_t* keep /*[dev n]*/, int32_t* repeated /*[dev 1]*/,
+                          void* stream);
+/* Stage 2: connected components of the rows of a k3 map nbr [27][n] (pcgc_kmap_k3 at stride 1; -1 = absent; 26-connectivity).  labels [n] =
+ * the smallest row of the row's component, sizes [n] = its row count; *n_components and *rounds (the launches of the labelling round, the
+ * one that changed nothing included) are HOST values.  Entries of the map that are no row of it are never followed.
+ * Rounds are launched by the host, which reads a device counter every few rounds; at most n + 1 of them (the argument is in clean.hip), -3
+ * when that cap is reached.  The call synchronises with `stream`. */
+int64_t pcgc_components_workspace_bytes(int64_t n);
+int pcgc_components(const int32_t* nbr /*[dev 27,n]*/, int64_t n, int32_t* labels /*[dev n]*/, int32_t* sizes /*[dev n]*/,
+                    int64_t* n_components /*host*/, int32_t* rounds /*host*/, void* workspace, size_t workspace_bytes, void* stream);
+/* labels_c / sizes_c [n_c] of the compacted survivors (keep1, prefix of pcgc_mask_scan, orig of pcgc_compact_index) -> labels [n] = INPUT
+ * row of the component's smallest row (-1 for a row keep1 drops), sizes [n] (0 for such a row) */
+int pcgc_clean_expand(const uint8_t* keep1, const int32_t* prefix, const int32_t* orig, const int32_t* labels_c, const int32_t* sizes_c,
+                      int64_t n, int64_t n_c, int32_t* labels, int32_t* sizes, void* stream);
+/* keep [n] = labels >= 0 and sizes >= min_component (>= 1) and, with keep_largest > 0, the row's component is one of the keep_largest
+ * largest of its batch item (ties to the smaller label; a 64-bit key per root, sorted).  coords [n,4] 16-byte aligned. */
+int64_t pcgc_clean_select_workspace_bytes(int64_t n);
+int pcgc_clean_select(const int32_t* coords, const int32_t* labels, const int32_t* sizes, int64_t n, int32_t min_component,
+                      int64_t keep_largest, uint8_t* keep /*[dev n]*/, void* workspace, size_t workspace_bytes, void* stream);
+/* out[prefix[i]] = colours[i] (three bytes a row) where mask[i] is set: pcgc_compact_coords for colours */
+int pcgc_clean_compact_colours(const uint8_t* colours /*[dev n,3]*/, const uint8_t* mask, const int32_t* prefix, int64_t n,
+                               uint8_t* out /*[dev total,3]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -205,6 +205,13 @@ SIGNATURES = {
     'pcgc_voxelize_heads': (ci, [vp, vp, i64, ci, vp, vp, vp, vp, sz, vp]),
     'pcgc_voxelize_merge_workspace_bytes': (i64, [i64]),
     'pcgc_voxelize_merge': (ci, [vp, vp, vp, i64, i64, vp, ci, vp, vp, vp, vp, vp, sz, vp]),
+    'pcgc_clean_neighbours': (ci, [vp, vp, i64, vp, vp, i64, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+    'pcgc_components_workspace_bytes': (i64, [i64]),
+    'pcgc_components': (ci, [vp, i64, vp, vp, vp, vp, vp, sz, vp]),
+    'pcgc_clean_expand': (ci, [vp, vp, vp, vp, vp, i64, i64, vp, vp, vp]),
+    'pcgc_clean_select_workspace_bytes': (i64, [i64]),
+    'pcgc_clean_select': (ci, [vp, vp, vp, i64, i32, i64, vp, vp, sz, vp]),
+    'pcgc_clean_compact_colours': (ci, [vp, vp, vp, i64, vp, vp]),
 }
 
 

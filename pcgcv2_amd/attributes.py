@@ -26,6 +26,7 @@ AttributeCoder.encode_batch / decode_batch code up to 16 frames in one pass over
     python -m pcgcv2_amd.attributes --filedir CLOUD.ply [MORE.ply ...] --qstep Q [--qstep_chroma Qc] [--outdir DIR]
                                     [--attribute_coder device [--chunk_steps S]]        (several files: one batch)
                                     [--voxelize B [--merge mean|first] [--devoxelize]]  (raw clouds: voxelised to B bits first, voxelize.py)
+                                    [--clean K,M [--clean_r2 R] [--keep_largest n]]     (outliers and fragments removed first, clean.py)
 """
 import os
 import struct
@@ -498,16 +499,22 @@ def main(argv=None):
                         "each to B bits first (voxelize.py; _vox.ply and _V.bin are written), then code _vox.ply")
     p.add_argument("--merge", choices=('mean', 'first'), default='mean', help="with --voxelize: the colour of a voxel, the mean of its points or its first point")
     p.add_argument("--devoxelize", action='store_true', help="with --voxelize: also write _dec_units.ply, the decoded cloud in the input's units (by _V.bin)")
+    from . import clean
+    clean.add_arguments(p)
     args = p.parse_args(argv)
     if args.voxelize is not None and not 1 <= args.voxelize <= 20:
         p.error(f'--voxelize {args.voxelize}: a bit depth in 1 .. 20')
     if args.devoxelize and args.voxelize is None:
         p.error('--devoxelize needs --voxelize')
+    clean.check_arguments(p, args)
     raw = []
     if args.voxelize is not None:                        # every raw cloud becomes its _vox.ply; the flow below takes those files
         from . import voxelize
         raw = [voxelize.in_front(f, args.outdir, args.voxelize, args.merge) for f in args.filedir]
         args.filedir = [vox for vox, _ in raw]
+    if args.clean is not None:                           # every voxelised cloud becomes its _clean.ply
+        args.filedir = [clean.in_front(f, args.outdir, args) for f in args.filedir]
+        raw = [(f, raw_prefix) for f, (_, raw_prefix) in zip(args.filedir, raw)]
     if len(args.filedir) == 1:
         run(args.filedir[0], args.outdir, args.qstep, args.qstep_chroma, args.attribute_coder, args.chunk_steps)
     else:

@@ -658,11 +658,14 @@ def _parse_cli(argv):
                         "to B bits first (voxelize.py; _vox.ply and _V.bin are written), then code _vox.ply; --res becomes 2^B")
     p.add_argument("--merge", choices=('mean', 'first'), default='mean', help="with --voxelize: the colour of a voxel, the mean of its points or its first point")
     p.add_argument("--devoxelize", action='store_true', help="with --voxelize: also write _dec_units.ply, the decoded cloud in the input's units (by _V.bin)")
+    from . import clean
+    clean.add_arguments(p)
     args = p.parse_args(argv)
     if args.voxelize is not None and not 1 <= args.voxelize <= 20:
         p.error(f'--voxelize {args.voxelize}: a bit depth in 1 .. 20')
     if args.devoxelize and args.voxelize is None:
         p.error('--devoxelize needs --voxelize')
+    clean.check_arguments(p, args)
     if args.attributes is not None:
         try:
             q = [int(v) for v in args.attributes.split(',')]
@@ -729,6 +732,9 @@ def main(argv=None):
         from . import voxelize
         args.filedir, raw_prefix = voxelize.in_front(args.filedir, args.outdir, args.voxelize, args.merge)
         args.res = 1 << args.voxelize
+    if args.clean is not None:                           # the voxelised cloud becomes _clean.ply, and that file is what is coded and measured
+        from . import clean
+        args.filedir = clean.in_front(args.filedir, args.outdir, args)
     if args.lossless:
         from . import lossless
         lossless.run(args.ckptdir, args.filedir, args.outdir, occupancy_coder=args.occupancy_coder, attributes=args.attributes,

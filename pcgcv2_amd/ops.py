@@ -2549,6 +2549,150 @@ def voxelize(points, colours=None, bits=10, origin=None, scale=None, merge='mean
     return Voxels(coords, counts, voxel_of, out, origin, scale, bits)
 
 
+# ------------------------------------------------------------------------------------------------ cleaning a voxelised cloud
+CLEAN_MAX_ROWS = 1 << 24
+Cleaned = namedtuple('Cleaned', 'keep neighbours labels sizes coords colours removed_density removed_component n_components rounds')
+
+
+def _clean_int(name, v, lo, hi=None):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
+        raise ValueError(f'clean: {name} {v!r}: an integer {"of at least " + str(lo) if hi is None else f"in {lo} .. {hi}"}')
+    return int(v)
+
+
+def _clean_coords(coords, who):
+    coords = coords.C if hasattr(coords, 'C') else coords
+    if not torch.is_tensor(coords) or not coords.is_cuda:
+        raise PcgcError(f'{who}: coords must be a ROCm device tensor (no CPU fallback exists)')
+    if coords.dtype != torch.int32 or coords.dim() != 2 or coords.shape[1] != 4:
+        raise ValueError(f'{who}: coords must be int32 [N,4], got {coords.dtype} {tuple(coords.shape)}')
+    if coords.shape[0] > CLEAN_MAX_ROWS:
+        raise ValueError(f'{who}: {coords.shape[0]} rows; at most 2^24')
+    coords = coords.contiguous()
+    if coords.shape[0]:
+        try:
+            check_coords(coords, who)
+        except PcgcError as e:
+            raise ValueError(str(e)) from None
+    return coords
+
+
+def _repeated(who, repeated, n):
+    if repeated:
+        raise ValueError(f'{who}: {repeated} of {n} rows repeat an earlier voxel; the rows must be distinct voxels')
+
+
+def clean_neighbours(coords, r2=16, min_neighbours=0, index=None):
+    """stage 1 of clean on rows that passed check_coords -> (neighbours int32 [N], keep1 uint8 [N], rows that repeat an earlier voxel)"""
+    n, dev = coords.shape[0], coords.device
+    index = D2Index(coords) if index is None else index
+    ball = _normals_ball(dev, r2)
+    neighbours = torch.empty(n, dtype=torch.int32, device=dev)
+    keep1 = torch.empty(n, dtype=torch.uint8, device=dev)
+    repeated = torch.empty(1, dtype=torch.int32, device=dev)
+    check(lib().pcgc_clean_neighbours(_p(index.qs), _p(index.perm), n, _p(index.cells.keys), _p(index.cells.vals), index.cells.cap,
+                                      _p(index.masks), _p(index.runlen), _p(ball), r2, min_neighbours, _p(neighbours), _p(keep1), _p(repeated),
+                                      _stream(coords)), 'clean_neighbours')
+    return neighbours, keep1, repeated
+
+
+def components(nbr):
+    """connected components of the rows of a k3 map nbr int32 [27, n] (-1 = absent): -> (labels int32 [n] = the smallest row of the row's
+    component, sizes int32 [n], number of components, rounds the labelling took)"""
+    _i32(nbr, 'nbr')
+    if nbr.dim() != 2 or nbr.shape[0] != 27:
+        raise PcgcError(f'components: the map must be [27, n], got {tuple(nbr.shape)}')
+    n, dev = nbr.shape[1], nbr.device
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    sizes = torch.empty(n, dtype=torch.int32, device=dev)
+    ws_bytes = int(lib().pcgc_components_workspace_bytes(n))
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+    n_components, rounds = ctypes.c_int64(0), ctypes.c_int32(0)
+    check(lib().pcgc_components(_p(nbr), n, _p(labels), _p(sizes), ctypes.byref(n_components), ctypes.byref(rounds), _p(ws), ws_bytes,
+                                _stream(nbr)), 'components')
+    return labels, sizes, int(n_components.value), int(rounds.value)
+
+
+def _components_of(coords, who, times=None, t0=0.0, distinct=False):
+    """hash + k3 map at stride 1 + components of distinct voxels (checked here unless the caller has) -> (labels, sizes, n_components, rounds)"""
+    n, dev = coords.shape[0], coords.device
+    if n == 0:
+        return torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev), 0, 0
+    table = HashTable(coords, 1)
+    if not distinct:
+        _repeated(who, n - int(mask_scan(first_occurrence_mask(coords, table))[1].item()), n)
+    nbr = kmap_k3(coords, 1, table)
+    t0 = tick_phase(times, 'map', t0, dev)
+    out = components(nbr)
+    tick_phase(times, 'components', t0, dev)
+    return out
+
+
+def connected_components(coords):
+    """stage 2 of clean on all rows: coords int32 [N,4] (batch, x, y, z), distinct voxels -> (labels int32 [N] = the smallest row of the row's
+    26-connected component, sizes int32 [N], number of components); clean(coords).rounds has the rounds the labelling took"""
+    coords = _clean_coords(coords, 'connected_components')
+    return _components_of(coords, 'connected_components')[:3]
+
+
+def clean(coords, colours=None, r2=16, min_neighbours=0, min_component=1, keep_largest=0, times=None):
+    """Outlier and fragment removal of a voxelised cloud (every output equals tests/clean_reference.py).  coords int32 [N,4]
+    (batch, x, y, z) device tensor of DISTINCT voxels, colours uint8 [N,3] or None.  Stage 1: neighbours = the other rows of the batch within
+    squared distance r2 (1 .. 64), keep1 = neighbours >= min_neighbours.  Stage 2: the 26-connected components of the survivors; labels = the
+    smallest input row of the row's component (-1 where stage 1 dropped the row), sizes = its rows (0 there); a row stays when its component
+    has min_component rows and, with keep_largest = n > 0, is one of the n largest of its batch item (ties to the smaller label).
+    -> Cleaned(keep bool [N], neighbours, labels, sizes int32 [N], coords [M,4], colours [M,3] or None (input order), removed_density,
+    removed_component, n_components, rounds).  ValueError naming the count for rows out of range and rows that repeat a voxel.  times
+    (measurement hook): a dict -> seconds of 'index', 'counts', 'map', 'components', 'select', 'compaction' and 'copies' added to it."""
+    r2 = _clean_int('r2', r2, 1, NORMALS_MAX_R2)
+    min_neighbours, min_component, keep_largest = _clean_int('min_neighbours', min_neighbours, 0, (1 << 31) - 1), \
+        _clean_int('min_component', min_component, 1, (1 << 31) - 1), _clean_int('keep_largest', keep_largest, 0, (1 << 31) - 1)
+    coords = _clean_coords(coords, 'clean')
+    n, dev = coords.shape[0], coords.device
+    if colours is not None:
+        if not torch.is_tensor(colours) or colours.device != dev or colours.dtype != torch.uint8 or tuple(colours.shape) != (n, 3):
+            raise ValueError(f'clean: colours must be uint8 [{n},3] on the device of the coordinates')
+        colours = colours.contiguous()
+    if n == 0:
+        e = lambda dt: torch.empty(0, dtype=dt, device=dev)
+        return Cleaned(e(torch.bool), e(torch.int32), e(torch.int32), e(torch.int32), coords, colours, 0, 0, 0, 0)
+    L, s = lib(), _stream(coords)
+    with torch.cuda.device(dev):
+        t0 = tick_phase(times, None, 0.0, dev)
+        index = D2Index(coords)
+        t0 = tick_phase(times, 'index', t0, dev)
+        neighbours, keep1, repeated = clean_neighbours(coords, r2, min_neighbours, index)
+        prefix, total = mask_scan(keep1)
+        t0 = tick_phase(times, 'counts', t0, dev)
+        repeated, n1 = torch.stack([repeated[0], total[0]]).cpu().tolist()
+        t0 = tick_phase(times, 'copies', t0, dev)
+        _repeated('clean', repeated, n)
+        del index
+        survivors, orig = compact_coords(coords, keep1, prefix, n1), compact_index(keep1, prefix, n1)
+        t0 = tick_phase(times, 'compaction', t0, dev)
+        labels_c, sizes_c, n_components, rounds = _components_of(survivors, 'clean', times, t0, distinct=True)
+        t0 = tick_phase(times, None, 0.0, dev)
+        labels = torch.empty(n, dtype=torch.int32, device=dev)
+        sizes = torch.empty(n, dtype=torch.int32, device=dev)
+        check(L.pcgc_clean_expand(_p(keep1), _p(prefix), _p(orig), _p(labels_c), _p(sizes_c), n, n1, _p(labels), _p(sizes), s), 'clean_expand')
+        keep = torch.empty(n, dtype=torch.uint8, device=dev)
+        ws_bytes = int(L.pcgc_clean_select_workspace_bytes(n))
+        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+        check(L.pcgc_clean_select(_p(coords), _p(labels), _p(sizes), n, min_component, keep_largest, _p(keep), _p(ws), ws_bytes, s), 'clean_select')
+        prefix, total = mask_scan(keep)
+        t0 = tick_phase(times, 'select', t0, dev)
+        m = int(total.item())
+        t0 = tick_phase(times, 'copies', t0, dev)
+        out = compact_coords(coords, keep, prefix, m)
+        out_colours = None
+        if colours is not None:
+            out_colours = torch.empty((m, 3), dtype=torch.uint8, device=dev)
+        if colours is not None and m:
+            check(L.pcgc_clean_compact_colours(_p(colours), _p(keep), _p(prefix), n, _p(out_colours), s), 'clean_compact_colours')
+        tick_phase(times, 'compaction', t0, dev)
+    return Cleaned(keep.view(torch.bool), neighbours, labels, sizes, out, out_colours, n - n1, n1 - m, n_components, rounds)
+
+
 # ------------------------------------------------------------------------------------------------ host codecs (numpy)
 def _np(a, dt):
     return np.ascontiguousarray(a, dtype=dt)

@@ -10,6 +10,7 @@ points that merge.
     4s magic "PCGV" | u32 version = 1 | u32 bits | 3 x f64 origin | f64 scale | u32 CRC-32 of all that precedes (ops.crc32)
 
     python -m pcgcv2_amd.voxelize --filedir raw.ply --bits 10 [--merge mean|first] [--out vox.ply] [--origin x,y,z --scale s]
+                                  [--clean K,M [--clean_r2 R] [--keep_largest n]]     (then cleaned into <out>_clean.ply, clean.py)
 """
 import math
 import os
@@ -189,6 +190,8 @@ def parser():
     p.add_argument('--out', default=None, help='output ASCII PLY (default: the input name + _vox.ply); the frame goes next to it as _V.bin')
     p.add_argument('--origin', type=parse_origin, default=None, help='x,y,z of voxel (0, 0, 0) instead of the per-axis minimum')
     p.add_argument('--scale', type=float, default=None, help='voxels per unit instead of (2^bits - 1) / the largest extent')
+    from . import clean
+    clean.add_arguments(p)
     return p
 
 
@@ -197,12 +200,17 @@ def main(argv=None):
     args = p.parse_args(argv)
     if not 1 <= args.bits <= 20:
         p.error(f'--bits {args.bits}: 1 .. 20')
+    from . import clean
+    clean.check_arguments(p, args)
     stem = os.path.splitext(args.filedir)[0]
     out = args.out or stem + '_vox.ply'
     prefix = os.path.splitext(out)[0]
     prefix = prefix[:-4] if prefix.endswith('_vox') else prefix
     v, n = voxelize_file(args.filedir, out, prefix + SUFFIX, args.bits, args.merge, args.origin, args.scale)
     print(describe(n, v))
+    if args.clean is not None:                           # `<prefix>_clean.ply` next to the voxelised file
+        print(clean.describe(clean.clean_file(out, os.path.splitext(out)[0] + '_clean.ply', args.clean_r2, args.clean[0], args.clean[1],
+                                              args.keep_largest)))
     return 0
 
 
