@@ -933,6 +933,27 @@ int pcgc_clean_select(const int32_t* coords, const int32_t* labels, const int32_
 int pcgc_clean_compact_colours(const uint8_t* colours /*[dev n,3]*/, const uint8_t* mask, const int32_t* prefix, int64_t n,
                                uint8_t* out /*[dev total,3]*/, void* stream);
 
+/* ---- Rendering a cloud into views (csrc/render.hip; the definition is tests/render_reference.py): a z-buffer splat.  Integers
+ *      only; every output is a function of the rows, their order and the matrices.  Buffers are the caller's; everything runs on `stream`. ---- */
+/* coords [n,4] (batch, x, y, z), 16-byte aligned, n = 0 .. 2^31 - 1, rows in any order; colours [n,3] or null (the depth shade); B items and V
+ * views, B V <= 64; H, W in 1 .. 4096; r in 0 .. 4 (a point covers (2 r + 1)^2 pixels); matrices [dev V,12] int64, Q16, row-major 3x4, which
+ * the caller has range-checked (|3x3| <= 2^20, |translation| <= 2^60, d inside int32 for coordinates below 2^21); planes [dev V,2] int32 = near,
+ * far of the depth shade; background = R | G << 8 | B << 16.  Outputs [B,V,H,W]: index (the winning row or -1), depth (d, 0 on background), mask
+ * (0 / 1), image [.,3].  bad [dev 1] = rows whose batch item is not below B or whose coordinates are not in [0, 2^21): they touch nothing and
+ * the caller refuses the cloud.  The workspace (one 64-bit word per item, view and pixel) is cleared on every call.  issued: null, or [dev 1]
+ * = the atomics the splat sent (a measurement; it depends on the order the threads ran in).  phases: 7; a sum of 1 clear, 2 splat, 4 resolve
+ * runs only those, on whatever the workspace holds (tools/render_time.py); bad and issued are zeroed by every call. */
+int64_t pcgc_render_splat_rows(void);
+int64_t pcgc_render_workspace_bytes(int B, int V, int H, int W);
+int pcgc_render(const int32_t* coords, const uint8_t* colours, int64_t n, int B, int V, int H, int W, int r, const int64_t* matrices,
+                const int32_t* planes, uint32_t background, int32_t* index, int32_t* depth, uint8_t* mask, uint8_t* image, int32_t* bad,
+                uint64_t* issued, int phases, void* workspace, size_t workspace_bytes, void* stream);
+/* two renderings of the same views, slices = B V of `pixels` pixels each -> sums [dev slices,8] uint64: pixels of the union U and of the
+ * intersection I of the masks, the SSE of R, G, B and of Y = (13933 R + 46871 G + 4732 B + 32768) >> 16 over U, the SSE of depth_a - depth_b
+ * over the pixels of I where it is below 2^19 in magnitude, and the number of pixels of I where it is not (the caller refuses those). */
+int pcgc_render_metric(const uint8_t* mask_a, const uint8_t* mask_b, const uint8_t* image_a, const uint8_t* image_b, const int32_t* depth_a,
+                       const int32_t* depth_b, int slices, int64_t pixels, uint64_t* sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

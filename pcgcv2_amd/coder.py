@@ -658,8 +658,11 @@ def _parse_cli(argv):
                         "to B bits first (voxelize.py; _vox.ply and _V.bin are written), then code _vox.ply; --res becomes 2^B")
     p.add_argument("--merge", choices=('mean', 'first'), default='mean', help="with --voxelize: the colour of a voxel, the mean of its points or its first point")
     p.add_argument("--devoxelize", action='store_true', help="with --voxelize: also write _dec_units.ply, the decoded cloud in the input's units (by _V.bin)")
-    from . import clean
+    from . import clean, render
     clean.add_arguments(p)
+    p.add_argument("--render", metavar='VIEWS', nargs='?', type=render.views_argument, const='faces', default=None,
+                   help="after decoding, render --filedir and _dec.ply into the same views (render.py: 'faces', 'turntable:N' or "
+                        "'yaw,pitch;...'), write _in_view<k>.png and _dec_view<k>.png and print the view PSNR, depth PSNR and IoU")
     args = p.parse_args(argv)
     if args.voxelize is not None and not 1 <= args.voxelize <= 20:
         p.error(f'--voxelize {args.voxelize}: a bit depth in 1 .. 20')
@@ -739,8 +742,12 @@ def main(argv=None):
         from . import lossless
         lossless.run(args.ckptdir, args.filedir, args.outdir, occupancy_coder=args.occupancy_coder, attributes=args.attributes,
                      attribute_coder=args.attribute_coder)
+        prefix = os.path.join(args.outdir, os.path.split(args.filedir)[-1].split('.')[0])
+        if args.render is not None:
+            from . import render
+            render.after_coding(args.filedir, prefix + '_dec.ply', prefix, args.render)
         if args.devoxelize:
-            voxelize.write_units(raw_prefix, os.path.join(args.outdir, os.path.split(args.filedir)[-1].split('.')[0]) + '_dec.ply')
+            voxelize.write_units(raw_prefix, prefix + '_dec.ply')
         return
     if args.attributes is not None and args.scaling_factor != 1:
         raise ValueError('--attributes codes colours on the decoded lattice: it does not combine with --scaling_factor')
@@ -789,6 +796,9 @@ def main(argv=None):
     print('D1 PSNR:\t', metrics["mseF,PSNR (p2point)"][0])
     if args.recolour or args.attributes is not None:
         print('Colour PSNR (Y):\t', colour['c[0],PSNRF'])
+    if args.render is not None:
+        from . import render
+        render.after_coding(args.filedir, prefix + '_dec.ply', prefix, args.render)
     if args.devoxelize:
         voxelize.write_units(raw_prefix, prefix + '_dec.ply')
 

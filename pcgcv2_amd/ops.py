@@ -2693,6 +2693,102 @@ def clean(coords, colours=None, r2=16, min_neighbours=0, min_component=1, keep_l
     return Cleaned(keep.view(torch.bool), neighbours, labels, sizes, out, out_colours, n - n1, n1 - m, n_components, rounds)
 
 
+# ------------------------------------------------------------------------------------------------ rendering a cloud into views
+RENDER_MAX_SLICES = 64                   # batch items x views
+RENDER_MAX_SIDE = 4096
+RENDER_MAX_R = 4
+RENDER_COORD_BITS = 21                   # coordinates lie in [0, 2^21)
+RENDER_METRIC_SUMS = ('union', 'intersection', 'sse_r', 'sse_g', 'sse_b', 'sse_y', 'sse_depth', 'depth_out_of_range')
+Rendered = namedtuple('Rendered', 'image depth index mask matrices')
+
+
+def render_splat_rows():
+    """rows per workgroup of the splat kernel"""
+    return int(lib().pcgc_render_splat_rows())
+
+
+def _render_int(name, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+        raise ValueError(f'render: {name} {v!r}: an integer in {lo} .. {hi}')
+    return int(v)
+
+
+def render(coords, colours, matrices, planes, B, H, W, r=0, background=(255, 255, 255), times=None):
+    """The z-buffer splat of csrc/render.hip (every output equals tests/render_reference.py).  coords int32 [N,4] (batch, x, y,
+    z) device tensor, batch below B, coordinates in [0, 2^21), rows in any order; colours uint8 [N,3] on the same device or None (the depth
+    shade); matrices int64 [V,3,4] in Q16 and planes int32 [V,2] (near, far of the depth shade), host arrays that pcgcv2_amd.render has built
+    and range-checked; B V <= 64; H, W in 1 .. 4096; r in 0 .. 4.  (u, v, d) = (M[:, :3] . p + M[:, 3]) >> 16; a row covers [u - r, u + r] x
+    [v - r, v + r]; a pixel keeps the smallest d, among equal d the smallest row.  -> Rendered(image uint8 [B,V,H,W,3], depth int32
+    [B,V,H,W], index int32 (the winning row or -1), mask bool, matrices int64 [V,3,4] on the device).  ValueError naming the count for rows
+    out of range.  times (measurement hook): a dict -> seconds of 'render' and 'copies' added to it."""
+    if not torch.is_tensor(coords) or not coords.is_cuda:
+        raise PcgcError('render: coords must be a ROCm device tensor (no CPU fallback exists)')
+    if coords.dtype != torch.int32 or coords.dim() != 2 or coords.shape[1] != 4:
+        raise ValueError(f'render: coords must be int32 [N,4], got {coords.dtype} {tuple(coords.shape)}')
+    n, dev = coords.shape[0], coords.device
+    if n >= 1 << 31:
+        raise ValueError(f'render: {n} rows; fewer than 2^31')
+    matrices = np.ascontiguousarray(matrices, dtype=np.int64)
+    if matrices.ndim != 3 or matrices.shape[1:] != (3, 4) or matrices.shape[0] < 1:
+        raise ValueError(f'render: matrices must be int64 [V,3,4], got {matrices.shape}')
+    V = matrices.shape[0]
+    planes = np.ascontiguousarray(planes, dtype=np.int32)
+    if planes.shape != (V, 2):
+        raise ValueError(f'render: planes must be int32 [{V},2], got {planes.shape}')
+    B = _render_int('B', B, 1, RENDER_MAX_SLICES)
+    if B * V > RENDER_MAX_SLICES:
+        raise ValueError(f'render: {B} items x {V} views = {B * V}; at most {RENDER_MAX_SLICES}')
+    H, W, r = _render_int('H', H, 1, RENDER_MAX_SIDE), _render_int('W', W, 1, RENDER_MAX_SIDE), _render_int('r', r, 0, RENDER_MAX_R)
+    bg = tuple(background) if isinstance(background, (tuple, list)) else ()
+    if len(bg) != 3:
+        raise ValueError(f'render: background {background!r}: three integers in 0 .. 255')
+    bg = [_render_int('background', v, 0, 255) for v in bg]
+    if colours is not None:
+        if not torch.is_tensor(colours) or colours.device != dev or colours.dtype != torch.uint8 or tuple(colours.shape) != (n, 3):
+            raise ValueError(f'render: colours must be uint8 [{n},3] on the device of the coordinates')
+        colours = colours.contiguous()
+    coords = coords.contiguous()
+    L, s = lib(), _stream(coords)
+    with torch.cuda.device(dev):
+        t0 = tick_phase(times, None, 0.0, dev)
+        m_dev = torch.from_numpy(matrices).to(dev)
+        p_dev = torch.from_numpy(planes).to(dev)
+        t0 = tick_phase(times, 'copies', t0, dev)
+        image = torch.empty((B, V, H, W, 3), dtype=torch.uint8, device=dev)
+        depth = torch.empty((B, V, H, W), dtype=torch.int32, device=dev)
+        index = torch.empty((B, V, H, W), dtype=torch.int32, device=dev)
+        mask = torch.empty((B, V, H, W), dtype=torch.uint8, device=dev)
+        bad = torch.empty(1, dtype=torch.int32, device=dev)
+        ws_bytes = int(L.pcgc_render_workspace_bytes(B, V, H, W))
+        ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+        check(L.pcgc_render(_p(coords) if n else None, _p(colours) if n else None, n, B, V, H, W, r, _p(m_dev), _p(p_dev),
+                            bg[0] | bg[1] << 8 | bg[2] << 16, _p(index), _p(depth), _p(mask), _p(image), _p(bad), None, 7, _p(ws), ws_bytes, s),
+              'render')
+        t0 = tick_phase(times, 'render', t0, dev)
+        bad = int(bad.item())
+        tick_phase(times, 'copies', t0, dev)
+    if bad:
+        raise ValueError(f'render: {bad} of {n} rows are outside the cube [0, 2^{RENDER_COORD_BITS}) or the {B} batch items')
+    return Rendered(image, depth, index, mask.view(torch.bool), m_dev)
+
+
+def render_metric(a, b):
+    """two Rendered of the same shape -> int64 [B,V,8] device tensor of the sums RENDER_METRIC_SUMS (include/pcgc_hip.h pcgc_render_metric)"""
+    for t, u, dt in ((a.image, b.image, torch.uint8), (a.depth, b.depth, torch.int32), (a.mask, b.mask, torch.bool)):
+        if not (torch.is_tensor(t) and t.is_cuda and torch.is_tensor(u) and u.device == t.device):
+            raise PcgcError('render_metric: both renderings must be on one ROCm device (no CPU fallback exists)')
+        if t.dtype != dt or u.dtype != dt or t.shape != u.shape or not t.is_contiguous() or not u.is_contiguous():
+            raise ValueError(f'render_metric: the renderings differ in shape or type ({tuple(t.shape)} {t.dtype}, {tuple(u.shape)} {u.dtype})')
+    Bn, V, H, W = a.depth.shape
+    if a.image.shape != (Bn, V, H, W, 3) or a.mask.shape != a.depth.shape or not 1 <= Bn * V <= RENDER_MAX_SLICES:
+        raise ValueError(f'render_metric: not a rendering: image {tuple(a.image.shape)}, depth {tuple(a.depth.shape)}, mask {tuple(a.mask.shape)}')
+    with torch.cuda.device(a.depth.device):
+        sums = torch.empty((Bn, V, len(RENDER_METRIC_SUMS)), dtype=torch.int64, device=a.depth.device)
+        check(lib().pcgc_render_metric(_p(a.mask), _p(b.mask), _p(a.image), _p(b.image), _p(a.depth), _p(b.depth), Bn * V, H * W, _p(sums),
+                                       _stream(a.depth)), 'render_metric')
+    return sums
+
+
 # ------------------------------------------------------------------------------------------------ host codecs (numpy)
 def _np(a, dt):
     return np.ascontiguousarray(a, dtype=dt)

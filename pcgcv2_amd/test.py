@@ -19,7 +19,12 @@ published figures computed from a dataset's own normals.  The host metric has no
 colour=True (`--colour`, off by default): the input's colours (red green blue) are carried onto every decoded cloud (pc_error.recolour_device
 with metric='device', sharing the two nearest-neighbour searches with D2; pc_error.recolour with metric='host'), `_dec.ply` is written with
 them, and the row gains the 36 colour columns of `pc_error_d -c 1` (pc_error.COLOUR_COLUMNS) — the colour distortion the geometry loss
-induces.  The columns are the same both ways.  An input without colours raises ValueError."""
+induces.  The columns are the same both ways.  An input without colours raises ValueError.
+
+views=VIEWS (`--views [VIEWS]`, off by default; metric='device' only): the projection metrics of render.py.  The input is
+rendered once into the views ('faces', 'turntable:N', 'yaw,pitch;...') of the cube [0, 2^ceil(log2 res))^3, every decoded cloud is rendered
+with the same matrices, and the row gains `view_depth_psnr` and `view_iou` and, with colour=True, `view_psnr_y` (the pictures then show the
+carried colours, else the depth shade): the figures of all views' sums added up."""
 import os
 import time
 
@@ -56,11 +61,14 @@ def _timed(fn):
     return out, round(time.time() - t0, 3)
 
 
-def sweep(filedir, ckpts, outdir, scaling_factor=1.0, rho=1.0, res=1024, metric='host', estimate_normals=None, colour=False):
+def sweep(filedir, ckpts, outdir, scaling_factor=1.0, rho=1.0, res=1024, metric='host', estimate_normals=None, colour=False, views=None):
     """Yield one single-row DataFrame per checkpoint (columns as in the reference's results/*.csv).  metric: 'host' or 'device',
-    estimate_normals: None or the squared radius R2, colour: carry the input's colours and report their distortion (module doc)."""
+    estimate_normals: None or the squared radius R2, colour: carry the input's colours and report their distortion, views: None or the view
+    list of the projection metrics (module doc)."""
     if metric not in ('host', 'device'):
         raise ValueError(f"metric must be 'host' or 'device', got {metric!r}")
+    if views is not None and metric != 'device':
+        raise ValueError("views (the projection metrics) are rendered on the GPU: use metric='device'")
     if colour and not ply_has_colours(filedir):
         raise ValueError(f'{filedir} has no colours (red green blue): colour=True needs them')
     estimated = estimate_normals is not None and not ply_has_normals(filedir)
@@ -79,6 +87,10 @@ def sweep(filedir, ckpts, outdir, scaling_factor=1.0, rho=1.0, res=1024, metric=
     if colour:                                    # the raw rows again, with their colours (duplicates included, as the metric reads them)
         c_xyz, c_rgb = read_ply_ascii_with_colours(filedir)
         ca_dev = torch.from_numpy(c_rgb).to(device) if metric == 'device' else None
+    if views is not None:                         # the input's pictures, once; every rate is rendered with their matrices
+        from . import render
+        view_bits = max(1, (int(res) - 1).bit_length())
+        view_in = render.render(a_dev, ca_dev if colour else None, views, bits=view_bits, batch_items=1)
     for rate, ckpt in enumerate(ckpts, start=1):
         model.load_state_dict(_state_dict(ckpt))
         coder = Coder(model=model, filename=prefix)
@@ -108,6 +120,12 @@ def sweep(filedir, ckpts, outdir, scaling_factor=1.0, rho=1.0, res=1024, metric=
                 mc = colour_psnr_device(a_dev, ca_dev, b_dev, cb_dev, nn=nn)
                 for k in COLOUR_COLUMNS:
                     row[k] = mc[k]
+            if views is not None:
+                view_dec = render.render(b_dev, cb_dev if colour else None, view_in.matrices, view_in.depth.shape[2:], view_bits, batch_items=1)
+                mv = render.view_metric(view_in, view_dec)['mean']
+                row['view_depth_psnr'], row['view_iou'] = mv['depth_psnr'], mv['iou']
+                if colour:
+                    row['view_psnr_y'] = mv['psnr_y']
         else:
             if colour:
                 write_ply_ascii_geo_rgb(dec_ply, dec_xyz, recolour(c_xyz, c_rgb, dec_xyz))
@@ -122,18 +140,20 @@ def sweep(filedir, ckpts, outdir, scaling_factor=1.0, rho=1.0, res=1024, metric=
 
 
 def test(filedir, ckptdir_list, outdir, resultdir, scaling_factor=1.0, rho=1.0, res=1024, verbose=True, metric='host', estimate_normals=None,
-         colour=False):
+         colour=False, views=None):
     """Reference entry point (test.py:13): runs the sweep, rewrites `<resultdir>/<cloud>.csv` after every rate.  metric: 'host' | 'device';
-    estimate_normals: None | R2; colour: False | True (module doc)."""
+    estimate_normals: None | R2; colour: False | True; views: None | a view list (module doc)."""
     os.makedirs(resultdir, exist_ok=True)
     csv_name = os.path.join(resultdir, os.path.split(filedir)[-1].split('.')[0] + '.csv')
     rows, table = [], None
-    for rate, row in enumerate(sweep(filedir, ckptdir_list, outdir, scaling_factor, rho, res, metric, estimate_normals, colour), start=1):
+    for rate, row in enumerate(sweep(filedir, ckptdir_list, outdir, scaling_factor, rho, res, metric, estimate_normals, colour, views), start=1):
         rows.append(row)
         table = pd.concat(rows, ignore_index=True)
         table.to_csv(csv_name, index=False)
         if verbose:
-            print(f'[r{rate}] bpp {row["bpp"][0]}  D1 {row["mseF,PSNR (p2point)"][0]:.4f} dB  enc {row["time(enc)"][0]} s  '
+            seen = '' if views is None else f'view depth {row["view_depth_psnr"][0]:.4f} dB  view IoU {row["view_iou"][0]:.6f}  ' + \
+                (f'view Y {row["view_psnr_y"][0]:.4f} dB  ' if colour else '')
+            print(f'[r{rate}] bpp {row["bpp"][0]}  D1 {row["mseF,PSNR (p2point)"][0]:.4f} dB  {seen}enc {row["time(enc)"][0]} s  '
                   f'dec {row["time(dec)"][0]} s  -> {csv_name}')
     return table
 
@@ -169,9 +189,15 @@ def main(argv=None):
                              'of squared radius R2 (1 .. 64, 16 when no value is given)')
     parser.add_argument("--colour", action='store_true',
                         help='carry the colours of the input onto every decoded cloud (written into _dec.ply) and report their distortion')
+    from . import render
+    parser.add_argument("--views", metavar='VIEWS', nargs='?', type=render.views_argument, const='faces', default=None,
+                        help="with --metric device: the projection metrics (render.py) over these views ('faces', 'turntable:N' or "
+                             "'yaw,pitch;...'): the columns view_depth_psnr and view_iou and, with --colour, view_psnr_y")
     args = parser.parse_args(argv)
+    if args.views is not None and args.metric != 'device':
+        parser.error('--views needs --metric device')
     table = test(args.filedir, args.ckpts, args.outdir, args.resultdir, scaling_factor=args.scaling_factor, rho=args.rho, res=args.res,
-                 metric=args.metric, estimate_normals=args.estimate_normals, colour=args.colour)
+                 metric=args.metric, estimate_normals=args.estimate_normals, colour=args.colour, views=args.views)
     name = os.path.split(args.filedir)[-1][:-4]
     try:
         plot_rd(table, name, os.path.join(args.resultdir, name + '.jpg'))
