@@ -332,7 +332,8 @@ __device__ __forceinline__ void child_tile_mainloop_mt(const int32_t* __restrict
 #pragma unroll
     for (int m = 0; m < MT; ++m) row_ok[m] = p0 + 16 * m + dma_r < n_p;
     // byte offset of each neighbour parent's first child row; absent -> a value no in-row offset can bring back into range (the
-    // entry point checks the tensor is smaller than ABSENT), so the per-cell address is ONE add and needs no select
+    // entry point checks that the tensor ends below ABSENT and that 7 row strides + 256 bytes fit above it: CHILD_COMMON_CHECKS), so
+    // the per-cell address is ONE add and needs no select
     constexpr unsigned ABSENT = 0xF0000000u;
     unsigned rowb[MT][V::NMAP];
 #pragma unroll
@@ -933,9 +934,16 @@ int launch_child_irn_b_split(const int32_t* pnbr, int64_t n_p, const float* in, 
 
 }  // namespace
 
+// The gathers encode an absent neighbour as byte offset ABSENT = 0xF0000000 and ADD to it, unconditionally, the child's row (at most
+// 7 row strides: child_tile_mainloop_mt's V::child(c) * row_bytes, Q4XTile's C.row_off * row_bytes) and the chunk inside the row (lane
+// offset <= 48, + 64 per 16-channel block <= 192 or a cell's byte_off, + the 16 bytes fetched: at most the 256 bytes of 64 channels).
+// The sum must stay in [ABSENT, 2^32), outside the resource: the tensor ends below ABSENT (first bound) and 7 strides + 256 bytes must
+// not carry past 2^32 (second bound: a row stride of at most 9 586 968 floats, 36.5 MiB).  Beyond it an absent neighbour would wrap
+// onto real rows.
 #define CHILD_COMMON_CHECKS(ROWS_LD)                                                                                           \
     PCGC_REQUIRE(parent_nbr && in && table, "null argument");                                                                  \
-    PCGC_REQUIRE(((ROWS_LD) & 3) == 0 && (((uintptr_t)in | (uintptr_t)table) & 15) == 0, "unaligned input");                 \
-    PCGC_REQUIRE(8 * n_parent * (int64_t)(ROWS_LD) * 4 < (int64_t)0xF0000000, "tensor too large for 32-bit buffer offsets"); \
+    PCGC_REQUIRE(((ROWS_LD) & 3) == 0 && (((uintptr_t)in | (uintptr_t)table) & 15) == 0, "unaligned input");                   \
+    PCGC_REQUIRE(8 * n_parent * (int64_t)(ROWS_LD) * 4 < (int64_t)0xF0000000, "tensor too large for 32-bit buffer offsets");   \
+    PCGC_REQUIRE(7 * (int64_t)(ROWS_LD) * 4 + 256 <= (int64_t)0x10000000, "row stride too large for 32-bit buffer offsets");   \
     PCGC_REQUIRE(table_bytes % 16 == 0, "table size");                                                                         \
     if (n_parent == 0) return 0;

@@ -26,7 +26,7 @@ namespace {
 template <class P, int MT, int D>
 struct Q4XTile {
     static constexpr auto S = P::template sched<MT, D>();
-    static constexpr unsigned ABSENT = 0xF0000000u;
+    static constexpr unsigned ABSENT = 0xF0000000u;            // + cell_off stays in [ABSENT, 2^32): the entry points' size and stride bounds
     static_assert(4 * MT * (D + 1) < 64, "vmcnt is 6 bits");
 
     // One tile: rows row0 + 64 m + lane.  pnbr [NMAP][n]; `in` rows of in_ld floats behind rs_in; ring: D slots of MT x 4 KB; acc out.
