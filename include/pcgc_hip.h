@@ -954,6 +954,31 @@ int pcgc_render(const int32_t* coords, const uint8_t* colours, int64_t n, int B,
 int pcgc_render_metric(const uint8_t* mask_a, const uint8_t* mask_b, const uint8_t* image_a, const uint8_t* image_b, const int32_t* depth_a,
                        const int32_t* depth_b, int slices, int64_t pixels, uint64_t* sums, void* stream);
 
+/* ---- Partition of a cloud into kd-tree blocks of at most max_num rows (csrc/partition.hip; the definition is
+ *      tests/partition_reference.py).  Integers only; every output equals the definition's.  Buffers are the caller's; everything runs on
+ *      `stream`, with which the call synchronises once per round.  A wrong argument, a null pointer or an undersized workspace is -2 before
+ *      anything is touched. ---- */
+#define PARTITION_MAX_BLOCKS 1024
+enum { PARTITION_INFO_ROUNDS, PARTITION_INFO_BLOCKS, PARTITION_INFO_OVERSIZE, PARTITION_INFO_BAD_RANGE, PARTITION_INFO_BAD_BATCH,
+       PARTITION_INFO_WOULD_BE, PARTITION_INFO_WORDS = 8 };
+enum { PARTITION_PHASE_BOUNDS, PARTITION_PHASE_COARSE, PARTITION_PHASE_CUT, PARTITION_PHASE_FINE, PARTITION_PHASE_ASSIGN, PARTITION_PHASE_ORDER,
+       PARTITION_PHASE_COPIES, PARTITION_PHASE_WORDS = 8 };
+/* coords [dev n,cols] int32, cols = 3 (x, y, z) or 4 (batch, x, y, z; batch 0), n = 0 .. 2^27, rows in any order and not necessarily distinct;
+ * max_num >= 1; align a power of two in 8 .. 1024.  -> block_of [dev n], perm [dev n] (the rows in block-major order, stable), table [dev
+ * 1024,8] of which the first `blocks` rows are written: (first_row, rows, lo_x, lo_y, lo_z, hi_x, hi_y, hi_z), the inclusive box of the block's
+ * voxels.  info [host 8]: rounds, blocks, oversize (blocks of more than max_num rows in one cell), then the counts behind a refusal.
+ * phase_seconds: null, or [host 8] to which the seconds of each phase are ADDED (a measurement hook: the call then waits for the stream after
+ * every phase).  Returns 0; -3 when rows have a coordinate outside [0, 2^20) or a batch index other than 0 (info names how many); -4 when block
+ * 1 025 would be created (info names the count the round would have left).  With -3 and -4 no output has been written. */
+int64_t pcgc_partition_workspace_bytes(int64_t n);
+int pcgc_partition(const int32_t* coords, int64_t n, int32_t cols, int64_t max_num, int32_t align, int32_t* block_of, int32_t* perm,
+                   int32_t* table, int64_t* info /*host*/, double* phase_seconds /*host or null*/, void* workspace, size_t workspace_bytes,
+                   void* stream);
+/* out [dev rows,4] (16-byte aligned) = (block_of - first_block, x, y, z) of the rows perm[first_row .. first_row + rows): the collated
+ * coordinates of a run of blocks, batch column = block - the run's first block */
+int pcgc_partition_gather(const int32_t* coords, int64_t n, int32_t cols, const int32_t* perm, const int32_t* block_of, int64_t first_row,
+                          int64_t rows, int32_t first_block, int32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ VARIANT = os.environ.get('PCGC_BUILD_VARIANT', '')
 OBJ = os.path.join(CSRC, '_obj' + ('_' + VARIANT if VARIANT else ''))
 LIB = os.path.join(HERE, 'libpcgc_hip' + ('_' + VARIANT if VARIANT else '') + '.so')
 SOURCES = ['coords.hip', 'select.hip', 'conv.hip', 'child_conv.hip', 'child_conv32.hip', 'child_cls_w.hip', 'child_irn.hip', 'child_irn_a16.hip', 'child_irn_b16.hip',
-           'child_irn_a32.hip', 'child_irn_b32.hip', 'child_q4.hip', 'rows_irn.hip', 'rows_q4.hip', 'conv_packed.hip', 'entropy.hip', 'loss.hip', 'occupancy.hip', 'rans_core.hip', 'occupancy_rans.hip', 'attribute_rans.hip', 'grad.hip', 'metric.hip', 'colour.hip', 'raht.hip', 'normals.hip', 'mesh.hip', 'collate.hip', 'voxelize.hip', 'clean.hip', 'render.hip', 'hostcodec.cpp', 'ply.cpp', 'mesh_io.cpp']
+           'child_irn_a32.hip', 'child_irn_b32.hip', 'child_q4.hip', 'rows_irn.hip', 'rows_q4.hip', 'conv_packed.hip', 'entropy.hip', 'loss.hip', 'occupancy.hip', 'rans_core.hip', 'occupancy_rans.hip', 'attribute_rans.hip', 'grad.hip', 'metric.hip', 'colour.hip', 'raht.hip', 'normals.hip', 'mesh.hip', 'collate.hip', 'voxelize.hip', 'clean.hip', 'render.hip', 'partition.hip', 'hostcodec.cpp', 'ply.cpp', 'mesh_io.cpp']
 HEADERS = [os.path.join(CSRC, 'pcgc_common.h'), os.path.join(CSRC, 'mfma_util.h'), os.path.join(CSRC, 'tile_sched.h'), os.path.join(CSRC, 'child_kernels.h'), os.path.join(CSRC, 'child_q4.h'), os.path.join(CSRC, 'q4x.h'), os.path.join(CSRC, 'q4x_sched.h'), os.path.join(CSRC, 'rows_q4_policy.h'), os.path.join(CSRC, 'eb_logits.h'), os.path.join(CSRC, 'occupancy_tables.h'), os.path.join(CSRC, 'rans_core.h'), os.path.join(HERE, '..', 'include', 'pcgc_hip.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fPIC', '-Wall', '-Wno-unused-result'] + \
         os.environ.get('PCGC_EXTRA_HIPCC_FLAGS', '').split()          # (experiments only, e.g. -DPCGC_EXP_...)

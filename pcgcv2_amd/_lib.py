@@ -212,6 +212,9 @@ SIGNATURES = {
     'pcgc_clean_select_workspace_bytes': (i64, [i64]),
     'pcgc_clean_select': (ci, [vp, vp, vp, i64, i32, i64, vp, vp, sz, vp]),
     'pcgc_clean_compact_colours': (ci, [vp, vp, vp, i64, vp, vp]),
+    'pcgc_partition_workspace_bytes': (i64, [i64]),
+    'pcgc_partition': (ci, [vp, i64, i32, i64, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'pcgc_partition_gather': (ci, [vp, i64, i32, vp, vp, i64, i64, i32, vp, vp]),
     'pcgc_render_splat_rows': (i64, []),
     'pcgc_render_workspace_bytes': (i64, [ci, ci, ci, ci]),
     'pcgc_render': (ci, [vp, vp, i64, ci, ci, ci, ci, ci, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, ci, vp, sz, vp]),

@@ -658,8 +658,9 @@ def _parse_cli(argv):
                         "to B bits first (voxelize.py; _vox.ply and _V.bin are written), then code _vox.ply; --res becomes 2^B")
     p.add_argument("--merge", choices=('mean', 'first'), default='mean', help="with --voxelize: the colour of a voxel, the mean of its points or its first point")
     p.add_argument("--devoxelize", action='store_true', help="with --voxelize: also write _dec_units.ply, the decoded cloud in the input's units (by _V.bin)")
-    from . import clean, render
+    from . import clean, partition, render
     clean.add_arguments(p)
+    partition.add_arguments(p)
     p.add_argument("--render", metavar='VIEWS', nargs='?', type=render.views_argument, const='faces', default=None,
                    help="after decoding, render --filedir and _dec.ply into the same views (render.py: 'faces', 'turntable:N' or "
                         "'yaw,pitch;...'), write _in_view<k>.png and _dec_view<k>.png and print the view PSNR, depth PSNR and IoU")
@@ -669,6 +670,7 @@ def _parse_cli(argv):
     if args.devoxelize and args.voxelize is None:
         p.error('--devoxelize needs --voxelize')
     clean.check_arguments(p, args)
+    partition.check_arguments(p, args)
     if args.attributes is not None:
         try:
             q = [int(v) for v in args.attributes.split(',')]
@@ -764,17 +766,26 @@ def main(argv=None):
     model.load_state_dict(torch.load(args.ckptdir, map_location=device)['model'])
     print('load checkpoint from \t', args.ckptdir)
 
-    coder = Coder(model=model, filename=prefix)
     scaled = args.scaling_factor != 1
     x_in = scale_sparse_tensor(x, factor=args.scaling_factor) if scaled else x
-    with _Stopwatch('Enc Time'):
-        coder.encode(x_in)
-    with _Stopwatch('Dec Time'):
-        x_dec = coder.decode(rho=args.rho)
+    if args.max_num is not None:                         # the cloud in kd-tree blocks (partition.py): x_dec is the blocks' decoded rows merged
+        from . import partition
+        coder = partition.BlockCoder(model, prefix, args.max_num, batch_items=args.block_batch)
+        with _Stopwatch('Enc Time'):
+            part = coder.encode(x_in)
+        with _Stopwatch('Dec Time'):
+            x_dec = coder.decode(rho=args.rho, roi=args.roi)
+        print(partition.describe(part))
+    else:
+        coder = Coder(model=model, filename=prefix)
+        with _Stopwatch('Enc Time'):
+            coder.encode(x_in)
+        with _Stopwatch('Dec Time'):
+            x_dec = coder.decode(rho=args.rho)
     if scaled:
         x_dec = scale_sparse_tensor(x_dec, factor=1.0 / args.scaling_factor)
 
-    bits = stream_bits(prefix)
+    bits = stream_bits(prefix) if args.max_num is None else partition.block_stream_bits(prefix)      # (in blocks: the four sums, then _P.bin)
     bpps = (bits / len(x)).round(3)                      # per-file rounding, then summed (coder.py:171-173)
     print('bits:\t', bits, '\nbpps:\t', bpps)
     print('bits:\t', sum(bits), '\nbpps:\t', sum(bpps).round(3))

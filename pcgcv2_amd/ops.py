@@ -2693,6 +2693,86 @@ def clean(coords, colours=None, r2=16, min_neighbours=0, min_component=1, keep_l
     return Cleaned(keep.view(torch.bool), neighbours, labels, sizes, out, out_colours, n - n1, n1 - m, n_components, rounds)
 
 
+# ------------------------------------------------------------------------------------------------ kd-tree blocks of a large cloud
+PARTITION_MAX_BLOCKS = 1024
+PARTITION_MAX_ROWS = 1 << 27
+PARTITION_ALIGNS = (8, 16, 32, 64, 128, 256, 512, 1024)
+PARTITION_PHASES = ('bounds', 'coarse', 'cut', 'fine', 'assign', 'order', 'copies')
+Partition = namedtuple('Partition', 'block_of perm table rounds oversize')
+
+
+def _partition_rows(coords, who):
+    """the rows of partition and partition_gather: a device tensor int32 [N,3] or [N,4], made contiguous"""
+    coords = coords.C if hasattr(coords, 'C') else coords
+    if not torch.is_tensor(coords) or not coords.is_cuda:
+        raise PcgcError(f'{who}: coords must be a ROCm device tensor (no CPU fallback exists)')
+    if coords.dtype != torch.int32 or coords.dim() != 2 or coords.shape[1] not in (3, 4):
+        raise ValueError(f'{who}: coords must be int32 [N,3] or [N,4], got {coords.dtype} {tuple(coords.shape)}')
+    if coords.shape[0] > PARTITION_MAX_ROWS:
+        raise ValueError(f'{who}: {coords.shape[0]} rows; at most 2^27')
+    return coords.contiguous()
+
+
+def partition(coords, max_num, align=8, times=None):
+    """kd-tree blocks of at most max_num rows (every output equals tests/partition_reference.py).  coords: device tensor int32
+    [N,3] (x, y, z) or [N,4] (batch 0, x, y, z), rows in any order, not necessarily distinct; align: a power of two in 8 .. 1024, no cell of
+    that size is shared by two blocks.  -> Partition(block_of int32 [N], perm int32 [N] (rows in block-major order, stable), table int32 [B,8]
+    = (first_row, rows, lo_x, lo_y, lo_z, hi_x, hi_y, hi_z), rounds, oversize).  ValueError naming the count for rows outside [0, 2^20), rows
+    of another batch item, more than 2^27 rows and more than 1 024 blocks.  times (measurement hook): a dict -> seconds of 'bounds', 'coarse',
+    'cut', 'fine', 'assign', 'order' and 'copies' added to it (the call then waits for the device after every phase)."""
+    if isinstance(max_num, bool) or not isinstance(max_num, (int, np.integer)) or max_num < 1:
+        raise ValueError(f'partition: max_num {max_num!r}: an integer of at least 1')
+    if isinstance(align, bool) or not isinstance(align, (int, np.integer)) or align not in PARTITION_ALIGNS:
+        raise ValueError(f'partition: align {align!r}: a power of two in 8 .. 1024')
+    coords = _partition_rows(coords, 'partition')
+    n, cols, dev = coords.shape[0], coords.shape[1], coords.device
+    max_num = min(int(max_num), (1 << 63) - 1)
+    if n == 0:                                                           # (no rows, no blocks: an empty tensor has no address to hand on)
+        e = torch.empty(0, dtype=torch.int32, device=dev)
+        return Partition(e, torch.empty(0, dtype=torch.int32, device=dev), torch.empty((0, 8), dtype=torch.int32, device=dev), 0, 0)
+    L = lib()
+    with torch.cuda.device(dev):
+        block_of = torch.empty(n, dtype=torch.int32, device=dev)
+        perm = torch.empty(n, dtype=torch.int32, device=dev)
+        table = torch.empty((PARTITION_MAX_BLOCKS, 8), dtype=torch.int32, device=dev)
+        ws_bytes = int(L.pcgc_partition_workspace_bytes(n))
+        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+        info = (ctypes.c_int64 * 8)()
+        seconds = None if times is None else (ctypes.c_double * 8)()
+        code = L.pcgc_partition(_p(coords), n, cols, max_num, int(align), _p(block_of), _p(perm), _p(table), info, seconds, _p(ws), ws_bytes,
+                                _stream(coords))
+    if code == -3:
+        if info[4]:
+            raise ValueError(f'partition: {info[4]} of {n} rows have a batch index other than 0')
+        raise ValueError(f'partition: {info[3]} of {n} rows are outside 0 .. 2^20 - 1')
+    if code == -4:
+        raise ValueError(f'partition: {info[5]} blocks; at most {PARTITION_MAX_BLOCKS} (a larger max_num gives fewer)')
+    check(code, 'partition')
+    if times is not None:
+        for j, phase in enumerate(PARTITION_PHASES):
+            times[phase] = times.get(phase, 0.0) + seconds[j]
+    return Partition(block_of, perm, table[:int(info[1])], int(info[0]), int(info[2]))
+
+
+def partition_gather(coords, part, first_block, blocks, table=None):
+    """the collated rows int32 [rows,4] of blocks first_block .. first_block + blocks - 1 of a Partition: (block - first_block, x, y, z), the
+    blocks contiguous and each in the input order of its rows.  table: the partition's table on the host (saves the copy)"""
+    coords = _partition_rows(coords, 'partition_gather')
+    n, dev = coords.shape[0], coords.device
+    table = part.table.cpu().numpy() if table is None else table
+    if blocks < 1 or first_block < 0 or first_block + blocks > len(table):
+        raise ValueError(f'partition_gather: blocks {first_block} .. {first_block + blocks - 1} of {len(table)}')
+    if len(part.perm) != n or len(part.block_of) != n:
+        raise ValueError(f'partition_gather: the partition is of {len(part.perm)} rows, the cloud has {n}')
+    first_row = int(table[first_block, 0])
+    rows = int(table[first_block:first_block + blocks, 1].sum())
+    out = torch.empty((rows, 4), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().pcgc_partition_gather(_p(coords), n, coords.shape[1], _p(part.perm), _p(part.block_of), first_row, rows, first_block, _p(out),
+                                          _stream(coords)), 'partition_gather')
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ rendering a cloud into views (DESIGN.md 8q)
 RENDER_MAX_SLICES = 64                   # batch items x views
 RENDER_MAX_SIDE = 4096
