@@ -1,234 +1,108 @@
-"""ctypes binding of libpcgc_hip.so (include/pcgc_hip.h).  There is NO fallback: if the HIP library is missing or a
-call fails, the product raises."""
+"""ctypes binding of libpcgc_hip.so, READ from include/pcgc_hip.h: the header is the only statement of the C ABI.  At import
+`parse_header` turns every prototype into a row of SIGNATURES, `typedef struct pcgc_collate_item` into CollateItem's fields and the integer
+`#define`s and anonymous enums into CONSTANTS; a new entry point needs its declaration in the header and nothing here.  Type rules: a
+parameter with `*` or `[` is c_void_p, except a `char` with exactly one `*` (c_char_p); a function-pointer typedef is c_void_p; the scalars
+are those of _SCALARS.  Anything else raises, naming the function.  There is NO fallback: if the HIP library is missing or a call fails,
+the product raises."""
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PCGC_LIB') or os.path.join(_HERE, 'libpcgc_hip.so')       # (PCGC_LIB: an experiment build, pcgcv2_amd/_build.py)
 
-vp, i64, i32, f32, sz = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_size_t
-ci = C.c_int
 
-# name -> (restype, argtypes); mirrors include/pcgc_hip.h one to one
-SIGNATURES = {
-    'pcgc_last_error': (C.c_char_p, []),
-    'pcgc_version': (ci, []),
-    'pcgc_hash_capacity': (i64, [i64]),
-    'pcgc_hash_clear': (ci, [vp, vp, i64, vp]),
-    'pcgc_hash_insert': (ci, [vp, i64, i32, vp, vp, i64, vp]),
-    'pcgc_hash_insert_policy': (ci, [vp, i64, i32, vp, vp, i64, ci, vp]),
-    'pcgc_set_convention': (ci, [ci, ci]),
-    'pcgc_hash_first_mask': (ci, [vp, i64, i32, vp, vp, i64, vp, vp, vp]),
-    'pcgc_coords_check_order': (ci, [vp, i64, vp, vp]),
-    'pcgc_coords_quantize': (ci, [vp, i64, i32, vp, vp]),
-    'pcgc_coords_children': (ci, [vp, i64, i32, vp, vp]),
-    'pcgc_coords_scale': (ci, [vp, i64, f32, vp, vp]),
-    'pcgc_scan_workspace_bytes': (sz, [i64]),
-    'pcgc_mask_scan': (ci, [vp, i64, vp, vp, vp, sz, vp]),
-    'pcgc_mask_scan_zeroed': (ci, [vp, i64, vp, vp, vp, sz, vp]),
-    'pcgc_compact_coords': (ci, [vp, vp, vp, i64, vp, vp]),
-    'pcgc_compact_feats': (ci, [vp, ci, ci, vp, vp, i64, vp, vp]),
-    'pcgc_kmap_k3': (ci, [vp, i64, i32, vp, vp, i64, vp, vp]),
-    'pcgc_kmap_k3_children': (ci, [vp, i64, vp, vp]),
-    'pcgc_kmap_k3_prune': (ci, [vp, i64, vp, vp, vp, i64, vp, vp]),
-    'pcgc_kmap_k3_prune_parent': (ci, [vp, i64, vp, vp, vp, i64, vp, vp]),
-    'pcgc_kmap_k3_from_coarse': (ci, [vp, i64, i32, vp, vp, vp, i64, vp, vp]),
-    'pcgc_down_maps': (ci, [vp, vp, vp, i64, i32, i64, vp, vp, vp]),
-    'pcgc_down_prepare': (ci, [vp, i64, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, sz, vp]),
-    'pcgc_down_finish': (ci, [vp, vp, vp, vp, vp, i64, i32, i64, vp, vp, vp, vp]),
-    'pcgc_down_level': (ci, [vp, i64, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp]),
-    'pcgc_pyramid_scratch_bytes': (sz, [i64, ci]),
-    'pcgc_pyramid': (ci, [vp, i64, i32, ci, vp, sz, vp, vp, vp, vp, vp]),
-    'pcgc_compact_index': (ci, [vp, vp, i64, vp, vp]),
-    'pcgc_conv_gather': (ci, [vp, ci, i64, vp, i64, ci, ci, ci, vp, vp, vp, ci, ci, ci, vp, ci, ci, ci, vp]),
-    'pcgc_conv_gather_unit': (ci, [vp, ci, i64, vp, vp, ci, vp, ci, ci, vp]),
-    'pcgc_conv_unit_from_coarse': (ci, [vp, i64, i32, vp, vp, vp, i64, vp, vp, ci, vp, ci, ci, vp]),
-    'pcgc_set_conv_impl': (ci, [ci]),
-    'pcgc_last_conv_impl': (ci, []),
-    'pcgc_set_up2_impl': (ci, [ci]),
-    'pcgc_irn_block': (ci, [vp, i64, vp, ci, ci, vp, vp, vp, ci, vp]),
-    'pcgc_irn_pass': (ci, [vp, i64, vp, ci, ci, vp, vp, vp, ci, ci, vp]),
-    'pcgc_conv_child': (ci, [vp, i64, vp, ci, ci, vp, i64, vp, vp, ci, ci, vp, ci, ci, vp]),
-    'pcgc_irn_child_pass': (ci, [vp, i64, ci, ci, vp, ci, vp, i64, vp, vp, vp, vp, ci, vp, ci, vp]),
-    'pcgc_irn_child_q4': (ci, [vp, i64, ci, ci, vp, ci, vp, i64, vp, vp, vp, vp, ci, vp, ci, vp]),
-    'pcgc_cls_child_q4': (ci, [vp, i64, vp, ci, ci, vp, i64, vp, vp, vp]),
-    'pcgc_conv_down_rows': (ci, [vp, i64, vp, i64, ci, ci, vp, i64, vp, ci, vp, ci, ci, vp]),
-    'pcgc_conv_rows': (ci, [vp, i64, vp, ci, ci, vp, i64, vp, vp, ci, ci, vp, ci, ci, vp]),
-    'pcgc_irn_rows_pass': (ci, [vp, i64, ci, ci, vp, ci, vp, i64, vp, vp, vp, vp, ci, vp, ci, vp]),
-    'pcgc_irn_rows_q4_pass': (ci, [vp, i64, ci, ci, vp, ci, vp, i64, vp, vp, vp, vp, ci, vp, ci, vp]),
-    'pcgc_set_rows_q4_variant': (ci, [ci]),
-    'pcgc_conv_packed64': (ci, [vp, i64, vp, ci, vp, i64, vp, ci, vp, ci, vp]),
-    'pcgc_set_packed_tuning': (ci, [ci, ci]),
-    'pcgc_set_sched_cus': (ci, [ci]),
-    'pcgc_last_sched': (ci, [vp]),
-    'pcgc_conv_up2': (ci, [i64, vp, ci, ci, vp, vp, ci, vp, ci, vp]),
-    'pcgc_conv_up2_gather': (ci, [i64, vp, ci, ci, vp, vp, vp, ci, vp, ci, vp]),
-    'pcgc_topk_workspace_bytes': (sz, [i64]),
-    'pcgc_topk_mask': (ci, [vp, ci, i64, i64, vp, vp, sz, vp]),
-    'pcgc_topk_mask_segments': (ci, [vp, ci, ci, vp, vp, vp, vp, sz, vp]),
-    'pcgc_topk_select_workspace_bytes': (sz, [i64]),
-    'pcgc_topk_select': (ci, [vp, ci, ci, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, sz, vp]),
-    'pcgc_kmap_k3_prune_sel': (ci, [vp, i64, vp, vp, vp, i64, vp, vp]),
-    'pcgc_kmap_k3_prune_parent_sel': (ci, [vp, i64, vp, vp, vp, i64, vp, vp]),
-    'pcgc_gather_rows_f32_ld': (ci, [vp, ci, ci, vp, i64, vp, vp]),
-    'pcgc_batch_counts': (ci, [vp, i64, vp, vp]),
-    'pcgc_sort_bzyx': (ci, [vp, i64, vp, vp, sz, vp]),
-    'pcgc_quantize_symbols_segments': (ci, [vp, ci, ci, vp, vp, vp, vp]),
-    'pcgc_sort_workspace_bytes': (sz, [i64]),
-    'pcgc_sort_zyx': (ci, [vp, i64, vp, vp, sz, vp]),
-    'pcgc_gather_rows_i32x4': (ci, [vp, vp, i64, vp, vp]),
-    'pcgc_gather_rows_f32': (ci, [vp, ci, vp, i64, vp, vp]),
-    'pcgc_relu': (ci, [vp, i64, vp, vp]),
-    'pcgc_add': (ci, [vp, vp, i64, vp, vp]),
-    'pcgc_round_minmax': (ci, [vp, i64, vp, vp]),
-    'pcgc_symbolize': (ci, [vp, i64, f32, vp, vp]),
-    'pcgc_desymbolize': (ci, [vp, i64, f32, vp, vp]),
-    'pcgc_quantize_symbols': (ci, [vp, i64, vp, vp, vp]),
-    'pcgc_cdf_table': (ci, [vp, ci, f32, f32, vp, vp, vp]),
-    'pcgc_loss_workspace_bytes': (sz, [i64]),
-    'pcgc_hash_contains': (ci, [vp, i64, vp, vp, i64, vp, vp, vp]),
-    'pcgc_eb_likelihood': (ci, [vp, ci, i64, ci, vp, f32, vp, vp, vp, sz, vp]),
-    'pcgc_neg_log2_sum': (ci, [vp, ci, i64, ci, vp, vp, sz, vp]),
-    'pcgc_bce_logits': (ci, [vp, i64, i64, vp, vp, vp, vp, vp, sz, vp]),
-    'pcgc_occ_workspace_bytes': (sz, [i64]),
-    'pcgc_occ_symbols': (ci, [vp, i64, i64, vp, vp, vp, vp, sz, vp]),
-    'pcgc_occ_tables': (ci, [vp, vp]),
-    'pcgc_occ_rans_workspace_bytes': (sz, [i64, ci]),
-    'pcgc_occ_rans_encode': (ci, [vp, i64, ci, vp, vp, sz, vp, vp, sz, vp]),
-    'pcgc_occ_rans_decode': (ci, [vp, i64, vp, i64, ci, vp, vp, vp, sz, vp]),
-    'pcgc_occ_symbols_segments': (ci, [vp, i64, ci, vp, vp, vp, vp, vp]),
-    'pcgc_occ_rans_batch_workspace_bytes': (i64, [i64, i64]),
-    'pcgc_occ_rans_encode_batch': (ci, [vp, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
-    'pcgc_occ_rans_decode_batch': (ci, [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
-    'pcgc_attr_rans_workspace_bytes': (i64, [i64, ci]),
-    'pcgc_attr_rans_encode': (ci, [vp, vp, vp, i64, ci, vp, sz, vp, vp, sz, vp]),
-    'pcgc_attr_rans_decode': (ci, [vp, vp, i64, vp, i64, ci, vp, vp, vp, sz, vp]),
-    'pcgc_conv_wgrad_workspace_bytes': (sz, [ci, i64, ci, ci]),
-    'pcgc_conv_wgrad_rows_per_group': (i64, [ci, i64, ci, ci]),
-    'pcgc_conv_wgrad': (ci, [vp, ci, i64, vp, i64, ci, ci, vp, ci, ci, vp, vp, vp, sz, vp]),
-    'pcgc_conv_up2_wgrad': (ci, [i64, vp, i64, ci, ci, vp, vp, ci, ci, vp, vp, vp, sz, vp]),
-    'pcgc_kmap_invert': (ci, [vp, ci, i64, i64, vp, vp]),
-    'pcgc_relu_bwd': (ci, [vp, ci, vp, ci, i64, ci, vp, ci, vp]),
-    'pcgc_scatter_rows': (ci, [vp, ci, ci, vp, i64, vp, i64, ci, vp]),
-    'pcgc_bce_logits_bwd': (ci, [vp, i64, i64, vp, C.c_double, vp, vp]),
-    'pcgc_eb_bwd_workspace_bytes': (sz, [i64, ci]),
-    'pcgc_eb_likelihood_bwd': (ci, [vp, ci, i64, ci, vp, f32, C.c_double, vp, vp, vp, sz, vp]),
-    'pcgc_d1_cell_masks': (ci, [vp, i64, vp, vp, i64, vp, i64, vp]),
-    'pcgc_d1_nn_cells': (ci, [vp, i64, vp, vp, i64, vp, vp, ci, i32, vp, vp, vp, vp]),
-    'pcgc_d1_nn': (ci, [vp, i64, vp, vp, i64, vp, ci, vp, vp, vp, vp]),
-    'pcgc_d2_runs': (ci, [vp, i64, vp, vp]),
-    'pcgc_d2_count': (ci, [vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, ci, i32, vp, vp, vp, vp, vp]),
-    'pcgc_d2_fill': (ci, [vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, ci, i32, vp, vp, vp, vp]),
-    'pcgc_d2_exhaustive': (ci, [vp, i64, vp, vp, i64, vp, ci, vp, vp, vp, vp, vp, vp]),
-    'pcgc_d2_scan_workspace_bytes': (sz, [i64]),
-    'pcgc_d2_scan': (ci, [vp, i64, vp, vp, sz, vp]),
-    'pcgc_d2_segment_lowest': (ci, [vp, i64, vp, i32, vp, vp]),
-    'pcgc_d2_recv_count': (ci, [vp, vp, i64, vp, i64, vp, vp]),
-    'pcgc_d2_recv_fill': (ci, [vp, vp, i64, vp, i64, vp, vp, vp, vp]),
-    'pcgc_d2_normals': (ci, [vp, vp, i64, vp, vp, vp, vp, vp, vp]),
-    'pcgc_d2_c2p': (ci, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
-    'pcgc_d2_reduce_workspace_bytes': (sz, []),
-    'pcgc_d2_reduce': (ci, [vp, vp, i64, vp, vp, vp, sz, vp]),
-    'pcgc_attr_transfer_workspace_bytes': (sz, [i64, i64, ci]),
-    'pcgc_attr_transfer': (ci, [vp, vp, vp, i64, vp, vp, vp, i64, vp, ci, vp, vp, sz, vp]),
-    'pcgc_colour_dist': (ci, [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp]),
-    'pcgc_colour_reduce_workspace_bytes': (sz, []),
-    'pcgc_colour_reduce': (ci, [vp, vp, i64, vp, vp, sz, vp]),
-    'pcgc_raht_tile_leaves': (i64, []),
-    'pcgc_raht_keys_workspace_bytes': (sz, [i64]),
-    'pcgc_raht_keys': (ci, [vp, i64, vp, vp, vp, vp, sz, vp]),
-    'pcgc_raht_tree_workspace_bytes': (sz, [i64]),
-    'pcgc_raht_tree': (ci, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
-    'pcgc_raht_forward': (ci, [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]),
-    'pcgc_raht_inverse': (ci, [vp, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]),
-    'pcgc_raht_quantize_workspace_bytes': (sz, [i64]),
-    'pcgc_raht_quantize': (ci, [vp, i64, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
-    'pcgc_raht_dequantize_workspace_bytes': (sz, [i64]),
-    'pcgc_raht_dequantize': (ci, [vp, vp, i64, i64, vp, vp, vp, ci, ci, vp, vp, vp, sz, vp]),
-    'pcgc_raht_keys_batch_workspace_bytes': (i64, [i64]),
-    'pcgc_raht_keys_batch': (ci, [vp, i64, ci, vp, vp, vp, vp, sz, vp]),
-    'pcgc_raht_tree_batch_workspace_bytes': (i64, [i64]),
-    'pcgc_raht_tree_batch': (ci, [vp, i64, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
-    'pcgc_raht_forward_batch': (ci, [vp, vp, i64, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]),
-    'pcgc_raht_inverse_batch': (ci, [vp, vp, vp, ci, vp, i64, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]),
-    'pcgc_raht_quantize_batch_workspace_bytes': (i64, [i64, ci]),
-    'pcgc_raht_quantize_batch': (ci, [vp, i64, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
-    'pcgc_raht_dequantize_batch_workspace_bytes': (i64, [i64, ci]),
-    'pcgc_raht_dequantize_batch': (ci, [vp, vp, i64, i64, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
-    'pcgc_attr_rans_batch_workspace_bytes': (i64, [i64, i64]),
-    'pcgc_attr_rans_encode_batch': (ci, [vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
-    'pcgc_attr_rans_decode_batch': (ci, [vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
-    'pcgc_normals_ball_masks': (i64, [i32, vp]),
-    'pcgc_normals_workspace_bytes': (sz, [i64]),
-    'pcgc_normals_estimate': (ci, [vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, i32, ci, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
-    'pcgc_set_normals_mapping': (ci, [ci]),
-    'pcgc_rc_encode': (i64, [vp, ci, ci, vp, i64, vp, i64]),
-    'pcgc_rc_decode': (ci, [vp, ci, ci, vp, i64, vp, i64]),
-    'pcgc_set_rc_impl': (ci, [ci]),
-    'pcgc_rc_encode_indexed': (i64, [vp, ci, ci, vp, i64, vp, i64, ci, vp]),
-    'pcgc_rc_decode_indexed': (ci, [vp, ci, ci, vp, i64, vp, i64, ci, vp]),
-    'pcgc_rc_encode_ctx': (i64, [vp, ci, ci, vp, vp, i64, vp, i64]),
-    'pcgc_rc_decode_ctx': (ci, [vp, ci, ci, vp, vp, i64, vp, i64]),
-    'pcgc_set_rc_threads': (ci, [ci]),
-    'pcgc_set_rc_lanes': (ci, [ci]),
-    'pcgc_set_oct_tiled': (ci, [ci]),
-    'pcgc_set_oct_model': (ci, [ci]),
-    'pcgc_oct_warm': (ci, []),
-    'pcgc_oct_encode': (i64, [vp, i64, vp, i64]),
-    'pcgc_oct_decode_count': (i64, [vp, i64]),
-    'pcgc_oct_decode': (ci, [vp, i64, vp, i64]),
-    'pcgc_items_encode': (ci, [ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci]),
-    'pcgc_items_probe': (ci, [ci, vp, vp, vp, vp, vp, vp]),
-    'pcgc_items_decode': (ci, [ci, vp, vp, ci, vp, vp, vp, vp, ci, vp, vp, ci, ci, ci]),
-    'pcgc_level_prepare_children': (ci, [vp, i64, i32, vp, vp, i64, vp, vp, vp, vp]),
-    'pcgc_frame_decode': (ci, [C.c_char_p, ci, vp, vp, ci, ci, i64, vp, vp, vp, vp, ci]),
-    'pcgc_frame_decode_begin': (ci, [C.c_char_p, ci, vp, vp, ci, ci, i64, vp, vp, vp, vp, ci]),
-    'pcgc_frame_decode_end': (ci, []),
-    'pcgc_frame_worker_test': (ci, [ci]),
-    'pcgc_table_cache': (ci, [ci]),
-    'pcgc_crc32': (C.c_uint32, [C.c_uint32, vp, i64]),
-    'pcgc_ply_read_ascii_geo': (i64, [C.c_char_p, vp, i64]),
-    'pcgc_ply_write_ascii_geo': (ci, [C.c_char_p, vp, i64]),
-    'pcgc_ply_write_ascii_geo_rgb': (ci, [C.c_char_p, vp, vp, i64]),
-    'pcgc_mesh_read': (ci, [C.c_char_p, vp, i64, vp, i64, vp]),
-    'pcgc_mesh_cdf_workspace_bytes': (sz, [i64]),
-    'pcgc_mesh_area_cdf': (ci, [vp, i64, vp, i64, vp, vp, vp, sz, vp]),
-    'pcgc_mesh_sample': (ci, [vp, i64, vp, vp, i64, C.c_uint64, C.c_uint64, i64, vp, vp, vp]),
-    'pcgc_mesh_voxelize_workspace_bytes': (sz, [i32]),
-    'pcgc_mesh_voxelize': (ci, [vp, i64, vp, vp, i64, C.c_uint64, i64, vp, i32, vp, i64, vp, vp, sz, vp]),
-    'pcgc_collate_rows': (ci, [vp, vp, ci, vp, vp, vp]),
-    'pcgc_voxelize_tile_rows': (i64, []),
-    'pcgc_voxelize_bounds_workspace_bytes': (i64, [i64]),
-    'pcgc_voxelize_bounds': (ci, [vp, ci, i64, vp, vp, vp, sz, vp]),
-    'pcgc_voxelize_quantize': (ci, [vp, ci, i64, ci, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]),
-    'pcgc_voxelize_heads_workspace_bytes': (i64, [i64]),
-    'pcgc_voxelize_heads': (ci, [vp, vp, i64, ci, vp, vp, vp, vp, sz, vp]),
-    'pcgc_voxelize_merge_workspace_bytes': (i64, [i64]),
-    'pcgc_voxelize_merge': (ci, [vp, vp, vp, i64, i64, vp, ci, vp, vp, vp, vp, vp, sz, vp]),
-    'pcgc_clean_neighbours': (ci, [vp, vp, i64, vp, vp, i64, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
-    'pcgc_components_workspace_bytes': (i64, [i64]),
-    'pcgc_components': (ci, [vp, i64, vp, vp, vp, vp, vp, sz, vp]),
-    'pcgc_clean_expand': (ci, [vp, vp, vp, vp, vp, i64, i64, vp, vp, vp]),
-    'pcgc_clean_select_workspace_bytes': (i64, [i64]),
-    'pcgc_clean_select': (ci, [vp, vp, vp, i64, i32, i64, vp, vp, sz, vp]),
-    'pcgc_clean_compact_colours': (ci, [vp, vp, vp, i64, vp, vp]),
-    'pcgc_partition_workspace_bytes': (i64, [i64]),
-    'pcgc_partition': (ci, [vp, i64, i32, i64, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
-    'pcgc_partition_gather': (ci, [vp, i64, i32, vp, vp, i64, i64, i32, vp, vp]),
-    'pcgc_render_splat_rows': (i64, []),
-    'pcgc_render_workspace_bytes': (i64, [ci, ci, ci, ci]),
-    'pcgc_render': (ci, [vp, vp, i64, ci, ci, ci, ci, ci, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, ci, vp, sz, vp]),
-    'pcgc_render_metric': (ci, [vp, vp, vp, vp, vp, vp, ci, i64, vp, vp]),
-}
+class PcgcError(RuntimeError):
+    pass
+
+
+_SCALARS = {'int': C.c_int, 'int32_t': C.c_int32, 'int64_t': C.c_int64, 'size_t': C.c_size_t, 'float': C.c_float, 'double': C.c_double,
+            'uint32_t': C.c_uint32, 'uint64_t': C.c_uint64}
+
+
+def _ctype(decl, callbacks, what):
+    """the ctypes class of one return type or parameter declaration (comments already stripped)"""
+    words = [w for w in re.findall(r'\w+', decl) if w != 'const']
+    if '*' in decl or '[' in decl:
+        return C.c_char_p if words[:1] == ['char'] and decl.count('*') == 1 and '[' not in decl else C.c_void_p
+    if words and words[0] in callbacks and len(words) <= 2:
+        return C.c_void_p
+    if not words or words[0] not in _SCALARS or len(words) > 2:                 # (two words: a type and the parameter's name)
+        raise PcgcError(f'{what}: `{" ".join(decl.split())}` is no type the binding knows ({", ".join(_SCALARS)}, pointers, arrays)')
+    return _SCALARS[words[0]]
+
+
+def parse_header(text, where='header'):
+    """C header text -> (signatures {name: (restype, argtypes)}, constants {name: int}, structs {name: _fields_})"""
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    text = re.sub(r'//[^\n]*', ' ', text)
+    constants = {m[1]: int(m[2]) for m in re.finditer(r'^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(-?\d+)[ \t]*$', text, re.M)}
+    text = re.sub(r'^[ \t]*#.*$', ' ', text, flags=re.M)
+
+    def enum(m):
+        value = 0
+        for item in filter(None, (s.strip() for s in m[1].split(','))):
+            name, _, explicit = (s.strip() for s in item.partition('='))
+            if explicit:
+                if not re.fullmatch(r'-?\d+', explicit):
+                    raise PcgcError(f'{where}: enumerator {name} = {explicit} is no integer the binding can read')
+                value = int(explicit)
+            constants[name] = value
+            value += 1
+        return ' '
+    text = re.sub(r'\benum\s*\{([^}]*)\}\s*;', enum, text)
+
+    structs = {}
+
+    def struct(m):
+        fields = []
+        for decl in filter(None, (s.strip() for s in m[2].split(';'))):
+            base, names = (decl.split(None, 1) + [''])[:2]
+            for name in (s.strip() for s in names.split(',')):
+                if base not in _SCALARS or not re.fullmatch(r'\w+', name):
+                    raise PcgcError(f'{where}: struct {m[1]}: `{decl}` is no field the binding knows')
+                fields.append((name, _SCALARS[base]))
+        structs[m[1]] = fields
+        return ' '
+    text = re.sub(r'\btypedef\s+struct\s+(\w+)\s*\{([^}]*)\}\s*\w+\s*;', struct, text)
+
+    callbacks = set()
+    text = re.sub(r'\btypedef\b[^;{}()]*\(\s*\*\s*(\w+)\s*\)\s*\([^()]*\)\s*;', lambda m: callbacks.add(m[1]) or ' ', text)
+
+    signatures = {}
+    for ret, name, args in re.findall(r'([\w\s*]+?)\s*\b(pcgc_\w+)\s*\(([^()]*)\)\s*;', text):
+        args = [] if args.strip() in ('', 'void') else args.split(',')
+        signatures[name] = (_ctype(ret, callbacks, f'{where}: return of {name}'),
+                            [_ctype(a, callbacks, f'{where}: argument {k} of {name}') for k, a in enumerate(args)])
+    unread = set(re.findall(r'\b(pcgc_\w+)\s*\(', text)) - set(signatures)
+    if unread:
+        raise PcgcError(f'{where}: the binding cannot read the declaration of {", ".join(sorted(unread))}')
+    return signatures, constants, structs
+
+
+def _read(header):
+    path = os.path.join(_HERE, '..', 'include', header)
+    if not os.path.exists(path):
+        raise PcgcError(f'{path} not found: the ctypes binding is read from it')
+    with open(path) as f:
+        return parse_header(f.read(), path)
+
+
+# name -> (restype, argtypes), {name: int} of the #defines and enums, {name: _fields_}: include/pcgc_hip.h as the compiler reads it
+SIGNATURES, CONSTANTS, _STRUCTS = _read('pcgc_hip.h')
+REFTABLE_SIGNATURES = _read('pcgc_reftable.h')[0]
 
 
 class CollateItem(C.Structure):
     """pcgc_collate_item of include/pcgc_hip.h"""
-    _fields_ = [('offset', i64), ('first_row', i32), ('rows', i32), ('width', i32), ('symmetry', i32), ('extent', i32), ('reserved', i32)]
+    _fields_ = _STRUCTS['pcgc_collate_item']
 
 
-class PcgcError(RuntimeError):
-    pass
+def _bind(l, signatures):
+    for name, (res, args) in signatures.items():
+        fn = getattr(l, name)
+        fn.restype, fn.argtypes = res, args
+    return l
 
 
 _lib = None
@@ -241,11 +115,7 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise PcgcError(f'{LIB_PATH} not found: run `python -c "import __graft_entry__ as g; g.build()"` '
                             '(hipcc --offload-arch=gfx950). The HIP library is mandatory; there is no fallback path.')
-        l = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(l, name)
-            fn.restype, fn.argtypes = res, args
-        _lib = l
+        _lib = _bind(C.CDLL(LIB_PATH), SIGNATURES)
     return _lib
 
 
@@ -254,18 +124,13 @@ _reftable = None
 
 
 def reftable_lib():
-    """libpcgc_reftable.so (csrc/reftable.cpp): int pcgc_reference_table(params, C, min_v, max_v, table_u16, cdf_f32)."""
+    """libpcgc_reftable.so (csrc/reftable.cpp), bound from include/pcgc_reftable.h"""
     global _reftable
     if _reftable is None:
         if not os.path.exists(REFTABLE_PATH):
             raise PcgcError(f'{REFTABLE_PATH} not found: run `python -c "import __graft_entry__ as g; g.build()"`')
         import torch  # noqa: F401  (libtorch_cpu must be loaded first)
-        l = C.CDLL(REFTABLE_PATH)
-        l.pcgc_reference_table.restype = ci
-        l.pcgc_reference_table.argtypes = [vp, ci, f32, f32, vp, vp]
-        l.pcgc_reference_table_clear.restype = ci
-        l.pcgc_reference_table_clear.argtypes = []
-        _reftable = l
+        _reftable = _bind(C.CDLL(REFTABLE_PATH), REFTABLE_SIGNATURES)
     return _reftable
 
 

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import roofline
-from ._lib import lib, check, PcgcError
+from ._lib import lib, check, PcgcError, CONSTANTS
 from .roofline import MFMA_F32_PEAK_TFLOPS, child_pairs, _halo_cells          # noqa: F401  (read as ops.<name> by bench.py, tools/ and tests)
 
 
@@ -2411,7 +2411,7 @@ def mesh_voxelize(verts, faces, cdf, seed, n, R, resolution):
 
 
 # ------------------------------------------------------------------------------------------------ data loader: batches out of the arena
-COLLATE_MAX_ITEMS = 16
+COLLATE_MAX_ITEMS = CONSTANTS['PCGC_COLLATE_MAX_ITEMS']
 
 
 def collate_rows(arena, items, out=None):
@@ -2694,10 +2694,12 @@ def clean(coords, colours=None, r2=16, min_neighbours=0, min_component=1, keep_l
 
 
 # ------------------------------------------------------------------------------------------------ kd-tree blocks of a large cloud
-PARTITION_MAX_BLOCKS = 1024
+PARTITION_MAX_BLOCKS = CONSTANTS['PARTITION_MAX_BLOCKS']
 PARTITION_MAX_ROWS = 1 << 27
 PARTITION_ALIGNS = (8, 16, 32, 64, 128, 256, 512, 1024)
-PARTITION_PHASES = ('bounds', 'coarse', 'cut', 'fine', 'assign', 'order', 'copies')
+PARTITION_PHASES = ('bounds', 'coarse', 'cut', 'fine', 'assign', 'order', 'copies')          # the header's PARTITION_PHASE_* enum, in its order
+if [CONSTANTS['PARTITION_PHASE_' + phase.upper()] for phase in PARTITION_PHASES] != list(range(CONSTANTS['PARTITION_PHASE_COPIES'] + 1)):
+    raise PcgcError('ops.PARTITION_PHASES does not follow the PARTITION_PHASE_* enum of include/pcgc_hip.h')
 Partition = namedtuple('Partition', 'block_of perm table rounds oversize')
 
 
@@ -2737,21 +2739,23 @@ def partition(coords, max_num, align=8, times=None):
         table = torch.empty((PARTITION_MAX_BLOCKS, 8), dtype=torch.int32, device=dev)
         ws_bytes = int(L.pcgc_partition_workspace_bytes(n))
         ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
-        info = (ctypes.c_int64 * 8)()
-        seconds = None if times is None else (ctypes.c_double * 8)()
+        info = (ctypes.c_int64 * CONSTANTS['PARTITION_INFO_WORDS'])()
+        seconds = None if times is None else (ctypes.c_double * CONSTANTS['PARTITION_PHASE_WORDS'])()
         code = L.pcgc_partition(_p(coords), n, cols, max_num, int(align), _p(block_of), _p(perm), _p(table), info, seconds, _p(ws), ws_bytes,
                                 _stream(coords))
+    rounds, blocks, oversize, bad_range, bad_batch, would_be = (int(info[CONSTANTS['PARTITION_INFO_' + word]]) for word in (
+        'ROUNDS', 'BLOCKS', 'OVERSIZE', 'BAD_RANGE', 'BAD_BATCH', 'WOULD_BE'))
     if code == -3:
-        if info[4]:
-            raise ValueError(f'partition: {info[4]} of {n} rows have a batch index other than 0')
-        raise ValueError(f'partition: {info[3]} of {n} rows are outside 0 .. 2^20 - 1')
+        if bad_batch:
+            raise ValueError(f'partition: {bad_batch} of {n} rows have a batch index other than 0')
+        raise ValueError(f'partition: {bad_range} of {n} rows are outside 0 .. 2^20 - 1')
     if code == -4:
-        raise ValueError(f'partition: {info[5]} blocks; at most {PARTITION_MAX_BLOCKS} (a larger max_num gives fewer)')
+        raise ValueError(f'partition: {would_be} blocks; at most {PARTITION_MAX_BLOCKS} (a larger max_num gives fewer)')
     check(code, 'partition')
     if times is not None:
         for j, phase in enumerate(PARTITION_PHASES):
             times[phase] = times.get(phase, 0.0) + seconds[j]
-    return Partition(block_of, perm, table[:int(info[1])], int(info[0]), int(info[2]))
+    return Partition(block_of, perm, table[:blocks], rounds, oversize)
 
 
 def partition_gather(coords, part, first_block, blocks, table=None):
@@ -2879,7 +2883,7 @@ def set_rc_impl(impl):
     check(lib().pcgc_set_rc_impl(int(impl)), 'set_rc_impl')
 
 
-RC_CKPT_WORDS = 6            # include/pcgc_hip.h PCGC_RC_CKPT_WORDS
+RC_CKPT_WORDS = CONSTANTS['PCGC_RC_CKPT_WORDS']
 
 
 def set_rc_threads(threads):
